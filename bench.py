@@ -9,7 +9,15 @@ layout (per-ego node_obs / adjacency). Multi-GPU: one process per GPU (torchrun)
 envs sharded by global index (weak scaling), RCCL all_reduce of the episode
 summary at each episode boundary, max-over-ranks timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line. --full adds what the
+headline figure does not need: the CPU baseline (the oracle on the host cores, "cpu_baseline" in the
+line, null without --full). --dump-outputs DIR writes what the last timed step handed its caller as
+DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed, seeded sample of the envs when the
+outputs are larger); seeds and actions are fixed, so two builds can be compared output for output.
+The files hold finite numbers only: the +inf that the info rows carry for agents that are done is
+written as 0, with its place kept in <name>_nonfinite.npy (dump_outputs).
 
 --gpus N > 1 starts N rank processes itself (or runs under torchrun, WORLD_SIZE = N). The timed
 window always straddles an episode boundary (auto-reset launch + RCCL episode summary): the
@@ -271,6 +279,70 @@ def timed_window(warmup, steps, epl):
     return warmup + (epl - (warmup + steps // 2) % epl) % epl
 
 
+DUMP_BUDGET = 64 * 10 ** 6   # --dump-outputs: bytes on disk, all files (and all ranks) together
+
+
+def step_outputs(env, buf):
+    """[(name, device tensor [n_envs, ...])]: what the last step handed its caller. Without --buffer
+    the tensors of GpuGraphVecEnv.step_wait()'s tuple and env.state(); with it the DeviceGraphBuffer row
+    that step filled and insert_step()'s return. Compact adjacency masks come as one 0/1 entry per
+    (ego, entity) rather than u64 words, which float64 could not hold."""
+    import torch
+    out = []
+    if buf is None:
+        out += [("obs", env.t_obs), ("agent_id", env.agent_id), ("node_obs", env.t_node), ("adj", env.t_adj),
+                ("rewards", env.t_rew)]
+        mask = env.t_adj_mask
+    else:
+        r = buf.step or buf.T   # the row the last insert_step selected (after_update copies row T to row 0)
+        out += [("obs", buf.obs[r]), ("share_obs", buf.share_obs[r]), ("agent_id", buf.agent_id[r]),
+                ("share_agent_id", buf.share_agent_id[r]), ("node_obs", buf.node_obs[r]), ("adj", buf.adj[r]),
+                ("rewards", buf.rewards[r - 1]), ("masks", buf.masks[r]), ("active_masks", buf.active_masks[r])]
+        mask = buf.adj_mask[r] if buf.adj_mask is not None else None
+    if mask is not None:
+        sh = torch.arange(64, device=mask.device, dtype=torch.int64)
+        out.append(("adj_mask", ((mask.unsqueeze(-1) >> sh) & 1).reshape(mask.shape[0], mask.shape[1], -1)[..., :env.E]))
+    out += [("dones", env.t_done), ("info", env.t_info), ("reset", env.t_reset), ("ep_info", env.t_epinfo),
+            ("state", env.t_state)]
+    return out
+
+
+def dump_outputs(path, outs, n_envs, rank, world):
+    """Write each output as float32 (float64 stays float64) to path/<name>.npy (ranks > 0:
+    <name>.rank<r>.npy). If together they exceed this rank's share of DUMP_BUDGET, every array keeps
+    the same sorted sample of envs, drawn with a fixed seed.
+
+    Every file holds finite numbers only, so that any comparison of two dumps is defined. The step's
+    info rows hold +inf by the reference's rules (min_relative_distance of an agent that is done,
+    core.py:696-709): an array with such entries is written with 0 in their place, next to
+    <name>_nonfinite.npy (float32, same shape: 0 finite, 1 +inf, 2 -inf, 3 NaN), which keeps what was
+    there. The sample leaves room for that file beside each float64 output, whatever the values."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    width = lambda t: 8 + 4 if t.dtype == torch.float64 else 4
+    per_env = sum(t[0].numel() * width(t) for _, t in outs)
+    keep = min(n_envs, max(1, (DUMP_BUDGET // world - 512 * len(outs)) // per_env))   # less the .npy headers
+    idx = None
+    if keep < n_envs:
+        idx = torch.as_tensor(np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False)),
+                              device=outs[0][1].device)
+    sfx = (".rank%d" % rank if rank else "") + ".npy"
+    names, nonfinite = [], {}
+    for name, t in outs:
+        t = t if idx is None else t.index_select(0, idx)
+        arr = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        names.append(name)
+        if not np.isfinite(arr).all():
+            code = np.where(np.isnan(arr), 3, np.where(np.isposinf(arr), 1, np.where(np.isneginf(arr), 2, 0)))
+            np.save(os.path.join(path, name + "_nonfinite" + sfx), code.astype(np.float32))
+            arr = np.where(code != 0, 0, arr).astype(arr.dtype)
+            names.append(name + "_nonfinite")
+            nonfinite[name] = int((code != 0).sum())
+        np.save(os.path.join(path, name + sfx), arr)
+    return {"dir": path, "envs": keep, "of": n_envs, "arrays": names, "nonfinite_entries": nonfinite}
+
+
 def dry_run(a, rank, world):
     """--dry-run: the multi-rank plumbing without a GPU (gloo): ranks, env offsets, the
     episode-summary collective and the max-over-ranks timing reduction."""
@@ -309,7 +381,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=250)
     ap.add_argument("--config", type=int, default=3, choices=sorted(CONFIGS))
     ap.add_argument("--envs", type=int, default=0, help="envs per GPU (default: config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (oracle on the "
+                         "host cores, 'cpu_baseline' in the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-cores", type=int, default=0)
     ap.add_argument("--buffer", action="store_true",
                     help="step through lsm.buffer.DeviceGraphBuffer: outputs written straight into "
@@ -346,7 +423,7 @@ def main():
     ep = 4  # curriculum ratio 1: the filter is active when requested (SURVEY finding 5)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         share, host = cpu_share()
         cores = a.cpu_cores or share
         epw, csteps = c.get("cpu_sample", (4, 500))
@@ -448,6 +525,7 @@ def main():
         elapsed = max(float(x[0]) for x in allt)
         kern_ms = max(float(x[1]) for x in allt)
     ep_summaries = summaries.results()   # after the timed region: the boundary's global summary
+    dumped = dump_outputs(a.dump_outputs, step_outputs(env, buf), n_envs, rank, world) if a.dump_outputs else None
     offsets = [rank * n_envs]
     if world > 1:
         o = torch.tensor([env.env_offset], dtype=torch.float64, device=dev)
@@ -493,6 +571,8 @@ def main():
             "cpu_baseline": cpu,
             "episode_summaries_timed": ep_summaries,
         }
+        if dumped:
+            line["outputs"] = dumped
         if a.edges:
             def more_steps(k):
                 # the window's pre-drawn actions again (the state has moved on; the step is the same work)

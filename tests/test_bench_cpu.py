@@ -33,6 +33,85 @@ def test_timed_window_straddles_an_episode_boundary():
         assert boundaries or k < 2, (w, k, epl, pre)
 
 
+def _fake_env(n, N=3, E=5, compact=False):
+    """Host tensors with the shapes and dtypes of GpuGraphVecEnv's outputs (values: a running index)."""
+    import types
+    import torch
+    fill = lambda shape, dt: torch.arange(int(torch.tensor(shape).prod()), dtype=torch.float64).reshape(shape).to(dt)
+    e = types.SimpleNamespace(E=E, t_obs=fill((n, N, 6), torch.float32), agent_id=fill((n, N, 1), torch.int64),
+                              t_node=fill((n, N, E, 7), torch.float32), t_rew=fill((n, N), torch.float32),
+                              t_done=fill((n, N), torch.float64) % 2 == 1, t_info=fill((n, N, 4), torch.float64),
+                              t_reset=fill((n,), torch.float64) % 3 == 0, t_epinfo=fill((n, 8), torch.float64),
+                              t_state=fill((n, N, 4), torch.float64))
+    e.t_adj = fill((n, E, E) if compact else (n, N, E, E), torch.float32)
+    e.t_adj_mask = torch.full((n, N, 1), 0b10010, dtype=torch.int64) if compact else None
+    return e
+
+
+def test_dump_outputs_names_dtypes_and_values(tmp_path):
+    """--dump-outputs: one .npy per output of the step, float64 outputs as float64 and every other
+    dtype as float32, values unchanged; a compact adjacency's mask words unpacked to 0/1 per entity."""
+    import numpy as np
+    env = _fake_env(4, compact=True)
+    info = bench.dump_outputs(str(tmp_path), bench.step_outputs(env, None), 4, 0, 1)
+    assert info["envs"] == info["of"] == 4
+    names = {"obs", "agent_id", "node_obs", "adj", "adj_mask", "rewards", "dones", "info", "reset", "ep_info", "state"}
+    assert set(info["arrays"]) == names == {p.name[:-4] for p in tmp_path.iterdir()}
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in names}
+    for k in ("info", "ep_info", "state"):
+        assert got[k].dtype == np.float64
+    for k in names - {"info", "ep_info", "state"}:
+        assert got[k].dtype == np.float32, k
+    np.testing.assert_array_equal(got["obs"], env.t_obs.numpy())
+    np.testing.assert_array_equal(got["state"], env.t_state.numpy())
+    np.testing.assert_array_equal(got["dones"], env.t_done.numpy().astype(np.float32))
+    assert got["adj_mask"].shape == (4, 3, 5) and (got["adj_mask"] == [0, 1, 0, 0, 1]).all()
+
+
+def test_dump_outputs_files_are_finite_and_keep_the_nonfinite_entries(tmp_path):
+    """The info rows hold +inf for agents that are done: every file written is finite, the entry is 0
+    in info.npy and its kind (1 +inf, 2 -inf, 3 NaN) stands in info_nonfinite.npy; arrays without
+    such entries get no such file."""
+    import numpy as np
+    env = _fake_env(4)
+    env.t_info[1, 2, 1] = float("inf")
+    env.t_info[3, 0, 1] = float("-inf")
+    env.t_info[0, 0, 3] = float("nan")
+    want = env.t_info.numpy().copy()
+    info = bench.dump_outputs(str(tmp_path), bench.step_outputs(env, None), 4, 0, 1)
+    assert info["nonfinite_entries"] == {"info": 3} and "info_nonfinite" in info["arrays"]
+    assert {p.name[:-4] for p in tmp_path.iterdir()} == set(info["arrays"])
+    assert [p.name for p in tmp_path.iterdir() if "nonfinite" in p.name] == ["info_nonfinite.npy"]
+    for p in tmp_path.iterdir():
+        assert np.isfinite(np.load(p)).all(), p.name
+    got, code = np.load(tmp_path / "info.npy"), np.load(tmp_path / "info_nonfinite.npy")
+    assert code.dtype == np.float32 and code.shape == got.shape and got.dtype == np.float64
+    assert (code[1, 2, 1], code[3, 0, 1], code[0, 0, 3], code.sum()) == (1, 2, 3, 6)
+    assert (got[code != 0] == 0).all()
+    np.testing.assert_array_equal(got[code == 0], want[code == 0])
+
+
+def test_dump_outputs_samples_within_the_budget(tmp_path, monkeypatch):
+    """Outputs larger than the budget: every array keeps the same sorted, seeded sample of envs (the
+    same from call to call), and the files together stay within the budget; ranks share it."""
+    import numpy as np
+    env = _fake_env(64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 20000)
+    a, b = tmp_path / "a", tmp_path / "b"
+    info = bench.dump_outputs(str(a), bench.step_outputs(env, None), 64, 0, 1)
+    bench.dump_outputs(str(b), bench.step_outputs(env, None), 64, 0, 1)
+    assert 1 <= info["envs"] < 64 and info["of"] == 64
+    assert sum(p.stat().st_size for p in a.iterdir()) <= 20000
+    for p in a.iterdir():
+        np.testing.assert_array_equal(np.load(p), np.load(b / p.name))
+    rows = np.load(a / "ep_info.npy")[:, 0] / 8          # ep_info[e, 0] = 8 e: the envs kept
+    assert len(rows) == info["envs"] and (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(np.load(a / "state.npy"), env.t_state.numpy()[rows.astype(int)])
+    half = bench.dump_outputs(str(tmp_path / "c"), bench.step_outputs(env, None), 64, 1, 2)
+    assert half["envs"] <= info["envs"] // 2 + 1
+    assert all(p.name.endswith(".rank1.npy") for p in (tmp_path / "c").iterdir())
+
+
 def test_multi_rank_launch_dry_run():
     """bench.py --gpus 2 starts two rank processes itself (no torchrun): each sees WORLD_SIZE=2, owns
     the env block [r * n, (r + 1) * n) and joins the episode-summary collective (gloo here)."""

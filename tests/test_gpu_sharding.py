@@ -75,6 +75,35 @@ def _bench(extra, timeout=400):
     return json.loads(lines[0])
 
 
+def test_gpu_bench_plain_run_dumps_repeatable_outputs(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps, runs no CPU baseline, and with
+    --dump-outputs writes the last timed step's outputs as finite float32 / float64 .npy files that a second
+    run with the same arguments reproduces bit for bit."""
+    def run(d):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+               "--envs", "64", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    one, two = run(tmp_path / "a"), run(tmp_path / "b")
+    assert one["steps"] == 20 and one["ms_per_step"] > 0 and one["cpu_baseline"] is None
+    assert one["value"] == pytest.approx(64 * 8 * 1e3 / one["ms_per_step"])
+    assert one["outputs"]["envs"] == one["outputs"]["of"] == 64
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == sorted(n + ".npy" for n in one["outputs"]["arrays"]) == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert {"obs.npy", "node_obs.npy", "adj.npy", "rewards.npy", "dones.npy", "state.npy"} <= set(names)
+    for nm in names:
+        x, y = np.load(tmp_path / "a" / nm), np.load(tmp_path / "b" / nm)
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 64 and np.isfinite(x).all(), nm
+        np.testing.assert_array_equal(x, y, err_msg=nm)
+    obs, state = np.load(tmp_path / "a" / "obs.npy"), np.load(tmp_path / "a" / "state.npy")
+    assert obs.shape[:2] == (64, 8) and np.isfinite(obs).all() and np.abs(obs).max() > 0
+    assert state.dtype == np.float64 and state.shape == (64, 8, 4) and np.abs(state).max() > 0
+
+
 def test_gpu_bench_two_ranks_gloo_on_one_gpu():
     """bench.py --gpus 2 with real GpuGraphVecEnvs (gloo, both ranks on cuda:0): the world size,
     the per-rank env offsets, max-over-ranks timing, and the episode summary reduced across the
