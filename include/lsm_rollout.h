@@ -194,7 +194,8 @@ void lsm_destroy(lsm_env* env);
  *   lanes_per_env      one-wave kernels: 64 (one env per wave, default; 0 = 64), 32 or 16 (2 / 4
  *                      envs per wave, needs num_agents <= lanes_per_env)
  *   team               -1 default (4 envs per workgroup for DI N = 8 and airtaxi N = 16), 0 the
- *                      plain one-wave kernel, 2 / 4 / 8 (team * num_agents <= 64)
+ *                      plain one-wave kernel, 2 / 4 / 8 (team * num_agents <= 64; an error where the
+ *                      configuration has no team kernel instantiation)
  *   generic            1: never the compile-time-N instantiations (default 0)
  *   lean               -1 default (airtaxi team kernel: lean LDS layout), 0: the full table
  *   filter_search      -1 default (1: bound-pruned exact argmin in the workgroup kernel), 0: full search
@@ -290,6 +291,15 @@ const char* lsm_build_id(void);
  * = 1248; values are clamped to [1, 1248]). A smaller stage makes every draw run out and take the
  * cooperative redraw (tests/test_gpu_parity.py). Applies from the next launch. */
 int lsm_test_set_mt_stage(lsm_env* env, int32_t words);
+
+/* Test-only: host copy of the value table's bounds blocks (the table the bound-pruned argmin reads):
+ * lo_hi float32 [blocks][2] = (lower, upper), blocks in C order over the per-dimension block counts,
+ * last dimension fastest; nblocks_per_dim[d] = ceil(cells_d / 2^bshift), 0 beyond the table's ndim;
+ * *bshift = log2 of the cells per dimension of a block. Nonzero when no value table is set or
+ * cap_blocks is below the block count (the counts and *bshift are filled in either way).
+ * Synchronises the device. tests/test_gpu_filter_search.py compares it with tests/hj_bounds_model.py. */
+int lsm_test_read_value_bounds(lsm_env* env, float* lo_hi, int32_t cap_blocks, int32_t nblocks_per_dim[5],
+                               int32_t* bshift);
 
 /* Shape helpers. */
 int32_t lsm_num_entities(const lsm_env* env);   /* E = N * (1 + L) */

@@ -3885,6 +3885,12 @@ int lsm_create_select(const lsm_config* cfg, const lsm_kernel_select* sel, lsm_e
     else if (g > 0 && e->team && g * N <= 64) e->team = g;
     else if (g > 0 && e->team) return fail(e, "kernel select: team * num_agents must be <= 64");
   }
+  // an explicit team size is honoured or refused: a parity test that asked for the team kernel
+  // and got rollout_kernel would pass without running it
+  if (e->sel.team > 0 && e->team != e->sel.team)
+    return fail(e, "kernel select: team > 0 needs a team kernel instantiation (double integrator N = 8 or "
+                   "airtaxi N = 16, 2 landmarks, lanes_per_env 64, num_internal_step <= 1, the training "
+                   "scenario, neither generic nor workgroup_per_env)");
   // lean LDS layout for the airtaxi team kernel (6 -> 8 envs per CU at N = 16);
   // sel.lean = 0 keeps the full table (A/B)
   e->lean = e->team && cfg->dynamics == LSM_AIRTAXI && (N & 3) == 0 && (e->E & 3) == 0;
@@ -4336,6 +4342,28 @@ int lsm_test_set_mt_stage(lsm_env* e, int32_t words) {
   if (!e) return 1;
   e->mt_stage = std::max(1, std::min(2 * MT_N, (int)words));
   e->params_dirty = true;
+  return 0;
+}
+
+int lsm_test_read_value_bounds(lsm_env* e, float* lo_hi, int32_t cap_blocks, int32_t nblocks_per_dim[5],
+                               int32_t* bshift) {
+  if (!e) return 1;
+  const TableDev& T = e->val;
+  if (!T.bnd || T.ndim < 1) return fail(e, "read value bounds: no value table set");
+  if (!lo_hi || !nblocks_per_dim || !bshift) return fail(e, "read value bounds: null argument");
+  const int B = 1 << T.bshift;
+  int64_t nblocks = 1;
+  for (int d = 0; d < 5; ++d) {
+    nblocks_per_dim[d] = 0;
+    if (d >= T.ndim) continue;
+    const int ncell = T.periodic[d] ? T.n[d] : T.n[d] - 1;
+    nblocks_per_dim[d] = (ncell + B - 1) / B;
+    nblocks *= nblocks_per_dim[d];
+  }
+  *bshift = T.bshift;
+  if ((int64_t)cap_blocks < nblocks) return fail(e, "read value bounds: capacity below the table's block count");
+  HIPCHK(e, hipDeviceSynchronize());
+  HIPCHK(e, hipMemcpy(lo_hi, T.bnd, (size_t)nblocks * sizeof(float2), hipMemcpyDeviceToHost));
   return 0;
 }
 

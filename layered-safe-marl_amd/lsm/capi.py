@@ -38,7 +38,7 @@ EXPORTED = ("lsm_create", "lsm_destroy", "lsm_last_error", "lsm_set_value_table"
             "lsm_buffer_last_error", "lsm_host_rk45_di", "lsm_host_glibc_pow", "lsm_action_errors",
             "lsm_kernel_name", "lsm_reset_layout", "lsm_layout_doubles", "lsm_host_philox_uniforms",
             "lsm_host_philox4x32", "lsm_episode_summary", "lsm_build_id", "lsm_test_set_mt_stage",
-            "lsm_create_select", "lsm_edges_scan_emit")
+            "lsm_create_select", "lsm_edges_scan_emit", "lsm_test_read_value_bounds")
 
 
 class LsmConfig(C.Structure):
@@ -131,6 +131,7 @@ def load_library(path: str = LIB_PATH):
         "lsm_episode_summary": (I32, [P, I32, P, P]),
         "lsm_build_id": (C.c_char_p, []),
         "lsm_test_set_mt_stage": (I32, [P, I32]),
+        "lsm_test_read_value_bounds": (I32, [P, P, I32, P, P]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

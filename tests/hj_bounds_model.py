@@ -1,0 +1,367 @@
+"""Numpy model of the HJ value-bounds table and of the bound-pruned argmin (test helper).
+
+The workgroup-per-env kernel (``rollout_block_kernel<D, 64, ...>``, csrc/lsm_block.h) finds each ego's
+deconflicting agent -- the argmin of the interpolated HJ value over the other active agents -- without
+looking up every pair: pass 1 reads a per-block (lower, upper) bound of the value (``bounds_kernel`` /
+``value_bounds``, csrc/lsm_rollout.hip), pass 2 looks up exact values only where the lower bound does
+not exceed the smallest upper bound U of the ego's in-grid pairs. This module restates
+
+* ``block_bounds``: the bounds table (bit for bit: float32, no contraction);
+* ``prune_stats``: which pairs the pruning drops for an oracle env's state, the exact argmin from the
+  oracle's own ``interpolate`` and the argmin the pruned search would return with the given bounds;
+* the hard tables (noise, spikes on block-boundary nodes) and the injected states of
+  tests/test_gpu_filter_search.py, with ``mutant`` bounds that forget the node a block shares with its
+  upper neighbour (or only the periodic wrap node) to prove those inputs can tell a wrong table.
+"""
+from __future__ import annotations
+
+import math
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "layered-safe-marl_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from lsm import hj_tables  # noqa: E402
+from oracle.hj_grid import Grid  # noqa: E402
+
+F32 = np.float32
+MARGIN = F32(4.0e-6)          # bounds_kernel's widening: 4e-6 max(|min|, |max|)
+SPIKE_DEPTH = F32(3.0)
+NOISE = 0.25
+
+
+def _periodic_mask(periodic, ndim):
+    per = np.zeros(ndim, dtype=bool)
+    for d in periodic:
+        per[d] = True
+    return per
+
+
+def block_node_sets(n, periodic, bshift, mutant=None):
+    """Node indices of every block along one dimension of n nodes: block b covers cells [b B, (b + 1) B)
+    clipped to the cell count, i.e. nodes b B .. min((b + 1) B, ncell), wrapped modulo n on a periodic
+    dimension. mutant "no_shared": nodes [b B, min((b + 1) B, ncell)) only (the node shared with the
+    next block, the last node and the wrap node are forgotten); "no_wrap": only the wrap node is."""
+    B = 1 << bshift
+    ncell = n if periodic else n - 1
+    out = []
+    for b in range((ncell + B - 1) // B):
+        hi_cell = min((b + 1) * B, ncell)
+        idx = np.arange(b * B, hi_cell + (0 if mutant == "no_shared" else 1))
+        if mutant == "no_wrap":
+            idx = idx[idx < n]
+        out.append(idx % n if periodic else idx)
+    return out
+
+
+def block_bounds(values, periodic, bshift, mutant=None, return_minmax=False):
+    """(lo_hi float32 [blocks][2], blocks per dimension) of a node table ``values`` (grid shape), blocks in
+    C order, last dimension fastest (TableDev::bstride). lo = mn - m, hi = mx + m with
+    m = float32(4e-6) * max(|mn|, |mx|), all float32. return_minmax adds the unwidened (mn, mx)."""
+    v = np.asarray(values, dtype=F32)
+    per = _periodic_mask(periodic, v.ndim)
+    mn, mx = v, v
+    for d in range(v.ndim):   # min / max over a box of nodes: one dimension after the other
+        sets = block_node_sets(v.shape[d], per[d], bshift, mutant)
+        mn = np.stack([np.take(mn, s, axis=d).min(axis=d) for s in sets], axis=d)
+        mx = np.stack([np.take(mx, s, axis=d).max(axis=d) for s in sets], axis=d)
+    nblocks = tuple(int(x) for x in mn.shape)
+    mn, mx = mn.reshape(-1).astype(F32), mx.reshape(-1).astype(F32)
+    m = (MARGIN * np.maximum(np.abs(mn), np.abs(mx))).astype(F32)
+    lo_hi = np.stack([(mn - m).astype(F32), (mx + m).astype(F32)], axis=1)
+    if return_minmax:
+        return lo_hi, nblocks, mn, mx
+    return lo_hi, nblocks
+
+
+def cell_index(grid, state):
+    """The cell Grid.corners interpolates in (lower node index per dimension), None outside the grid."""
+    s32 = np.asarray(state, dtype=np.float64).astype(F32)
+    pos = (s32 - grid.lo32) / grid.sp32
+    cell = np.zeros(grid.ndim, dtype=np.int64)
+    for d in range(grid.ndim):
+        p = pos[d]
+        if not np.isfinite(p):
+            return None
+        n = grid.shape[d]
+        f = int(np.floor(p))
+        if grid.periodic[d]:
+            cell[d] = f % n
+        else:
+            if p < F32(0.0) or p > F32(n - 1):
+                return None
+            cell[d] = min(f, n - 2)
+    return cell
+
+
+def flat_block(cell, bshift, nblocks):
+    return int(np.ravel_multi_index(tuple(np.asarray(cell) >> bshift), nblocks))
+
+
+def pair_table(env, egos=None):
+    """Every candidate pair of oracle env ``env`` as _filter_one sees it: per ego the other active agents
+    in index order with the pair's cell (None outside the grid) and its exact value (oracle interpolate,
+    +inf outside). Independent of the bounds' block size."""
+    act = [j for j in range(env.N) if not env.done[j] and env.departed[j]]
+    out = {}
+    for i in (act if egos is None else egos):
+        rows = []
+        for j in act:
+            if j == i:
+                continue
+            rel = env._rel_state(env.s[i], env.s[j])
+            cell = cell_index(env.hj_grid, rel)
+            v, ok = env._value(rel)
+            assert ok == (cell is not None)
+            rows.append((j, cell, F32(v) if ok else F32(np.inf)))
+        out[i] = rows
+    return out
+
+
+def prune_stats(env, table, bshift, bounds=None, pairs=None, egos=None):
+    """Pruning of oracle env ``env``'s current state with the bounds of ``table`` (an HjTable; None: the
+    env's own, separation-shifted values) at block size 2^bshift, or with explicit ``bounds`` (a
+    block_bounds result, e.g. a mutant's). Per ego U = the smallest upper bound over its in-grid pairs;
+    a pair is out of grid, pruned (lower bound > U) or surviving. Returns counts, the pruned share of
+    in-grid pairs, per ego the exact argmin (first occurrence, as np.argmin in _filter_one) and the
+    argmin of the pruned search (out-of-grid pairs count as +inf, pruned pairs are skipped)."""
+    if bounds is None:
+        vals = env.values_hj if table is None else table.values_hj
+        bounds = block_bounds(vals, np.flatnonzero(env.hj_grid.periodic), bshift)
+    lo_hi, nblocks = bounds[0], bounds[1]
+    pairs = pair_table(env, egos) if pairs is None else pairs
+    st = dict(n_pairs=0, n_out=0, n_in=0, n_pruned=0, n_survive=0, egos_all_out=0, argmin={}, pruned_argmin={},
+              upper={}, min_value={}, bound_violations=0)
+    for i, rows in pairs.items():
+        blk = [None if c is None else flat_block(c, bshift, nblocks) for _, c, _ in rows]
+        U = min([lo_hi[b, 1] for b in blk if b is not None], default=F32(np.inf))
+        st["upper"][i] = U
+        best = pbest = None
+        for (j, c, v), b in zip(rows, blk):
+            st["n_pairs"] += 1
+            if best is None or v < best[1]:
+                best = (j, v)
+            if b is None:
+                st["n_out"] += 1
+            else:
+                st["n_in"] += 1
+                if not (lo_hi[b, 0] <= v <= lo_hi[b, 1]):
+                    st["bound_violations"] += 1
+                if lo_hi[b, 0] > U:
+                    st["n_pruned"] += 1
+                    continue
+                st["n_survive"] += 1
+            if pbest is None or v < pbest[1]:
+                pbest = (j, v)
+        if rows:
+            st["argmin"][i], st["min_value"][i] = best
+            st["pruned_argmin"][i] = pbest[0]
+            st["egos_all_out"] += all(b is None for b in blk)
+    st["share"] = st["n_pruned"] / max(1, st["n_in"])
+    return st
+
+
+# ---- tables -------------------------------------------------------------------------------------
+DI_SMALL, DI_WIDE = (31, 31, 21, 21), (131, 127, 4, 3)
+AT_SMALL, AT_WIDE = (25, 25, 24, 7, 7), (57, 53, 44, 4, 3)
+
+
+def spike_nodes(dyn, shape, bshift):
+    """Spiked nodes of a table for blocks of B = 2^bshift cells, each on a block boundary and where the
+    smooth value is large (far relative position, nobody closing): name -> (node index, dimension,
+    sides), sides being the cells next to the node along that dimension that an injected pair visits.
+      shared: index k B of dimension 0, shared by blocks k - 1 and k;
+      last:   the last node of non-periodic dimension 1 (the clipped last block's top node);
+      wrap:   node 0 of the periodic heading dimension, which the last block reaches by wrapping."""
+    B = 1 << bshift
+    n0, n1 = shape[0], shape[1]
+    k0 = B * max(1, int(round(0.12 * (n0 - 1) / B)))   # x well on the negative side, |x| large
+    mid0, mid1 = (n0 - 1) // 2 + 1, (n1 - 1) // 2 + 1   # x, y just above 0
+    if dyn == "double_integrator":
+        rest = tuple(int(math.ceil((n - 1) / 2)) for n in shape[2:])   # relative velocity at or just above 0
+        return {"shared": ((k0, mid1) + rest, 0, ("below", "above")),
+                "last": ((mid0, n1 - 1) + rest, 1, ("below",))}
+    nth = shape[2]
+    va, vb = shape[3] - 2, 1    # the ego faster than the other: with the other behind, the pair recedes
+    return {"shared": ((k0, mid1, nth // 2, va, vb), 0, ("below", "above")),
+            "last": ((mid0, n1 - 1, nth // 2, va, vb), 1, ("below",)),
+            "wrap": ((k0, mid1, 0, va, vb), 2, ("below", "above"))}
+
+
+def make_table(dyn, kind, shape, separation=None, bshift=None, seed=7):
+    """The project's synthetic value table of ``shape`` as HjDataHandle builds it, then ``kind``:
+    "smooth" as it is, "rough" plus uniform(+-0.25) noise per node, "spike" with the nodes of
+    spike_nodes(dyn, shape, bshift) lowered by 3.0. Gradients recomputed from the final values."""
+    di = dyn == "double_integrator"
+    st = hj_tables.synthetic_di_stored(shape) if di else hj_tables.synthetic_airtaxi_stored(shape)
+    sep = st["separation_distance"] if separation is None else separation
+    t = hj_tables.value_table_from_stored(st, sep)
+    v = t.values_hj.copy()
+    if kind == "rough":
+        v = (v + np.random.default_rng(seed).uniform(-NOISE, NOISE, v.shape).astype(F32)).astype(F32)
+    elif kind == "spike":
+        for node, _, _ in spike_nodes(dyn, shape, bshift).values():
+            v[node] = F32(v[node] - SPIKE_DEPTH)
+    else:
+        assert kind == "smooth", kind
+    t.values_hj = v
+    t.grads_hj = hj_tables.grad_values(v, t.lo, t.hi, t.shape, t.periodic)
+    t.extra["kind"] = kind
+    return t
+
+
+def node_coords(table, node):
+    sp = table.spacings
+    return np.asarray(table.lo, dtype=np.float64) + sp * np.asarray(node, dtype=np.float64)
+
+
+# ---- injected states ------------------------------------------------------------------------------
+def _states_from_rel(dyn, rel, crowd_rels, N):
+    """Agent states [N][4] with ego 0, partner 1 at relative state ``rel`` and agents 2.. at crowd_rels
+    (the oracle's _rel_state conventions; the airtaxi ego heads along +x at the origin)."""
+    s = np.zeros((N, 4))
+    rels = [rel] + list(crowd_rels)
+    if dyn == "double_integrator":
+        # rel = ego - other (positions and velocities); velocities split evenly around zero
+        ev = 0.5 * np.asarray(rel[2:4])
+        s[0] = [0.0, 0.0, ev[0], ev[1]]
+        for k, r in enumerate(rels):
+            s[1 + k] = [-r[0], -r[1], ev[0] - r[2], ev[1] - r[3]]
+    else:
+        # rel = (other - ego in the ego's frame, heading difference, ego speed, other speed)
+        s[0] = [0.0, 0.0, 0.0, rel[3]]
+        for k, r in enumerate(rels):
+            s[1 + k] = [r[0], r[1], r[2], r[4]]
+    return s
+
+
+def spike_layout(dyn, table, spike, side, N, crowd_dist, eps=0.03):
+    """One env's states for a spike pair: ego 0 and partner 1 with their relative state ``eps`` of a cell
+    inside the cell just below / above the spiked node along the spike's dimension (and just above the
+    node in the others), the other N - 2 agents a tight crowd at relative distance ~crowd_dist on the
+    far side of the ego, moving like the ego (their pairs neither close nor recede)."""
+    node, dim, _ = spike
+    sp = table.spacings
+    rel = node_coords(table, node) + eps * sp
+    rel[dim] = node_coords(table, node)[dim] + (-eps if side == "below" else eps) * sp[dim]
+    if dim in table.periodic and side == "below":
+        rel[dim] += table.hi[dim] - table.lo[dim]   # node 0 seen from the last cell: just under +pi
+    m = N - 2
+    a, b = np.divmod(np.arange(m), 8)
+    # away from the partner (which sits at x < 0 in both conventions' relative frame)
+    cx, cy = crowd_dist + 0.04 * a, 0.04 * (b - 3.5)
+    if dyn == "double_integrator":
+        crowd = [np.array([cx[k], cy[k], 0.5 * rel[2], 0.5 * rel[3]]) for k in range(m)]
+    else:
+        # off the lattice and off heading 0: with rows of agents exactly abreast or in line, relative
+        # coordinates and HJ gradients are exact zeros on one side of the comparison and 1e-16 on the
+        # other (d sin(atan2(..) - theta) against a rotation), and their sign picks the filter's control
+        jit = np.random.default_rng(12).uniform(-1.0, 1.0, (m, 3))
+        crowd = [np.array([cx[k] + 0.012 * jit[k, 0], cy[k] + 0.012 * jit[k, 1], 0.03 + 0.02 * jit[k, 2], rel[3],
+                           rel[3]]) for k in range(m)]
+    return _states_from_rel(dyn, rel, crowd, N)
+
+
+def loner_layout(dyn, table, N):
+    """Every agent clustered in one corner except agent 0 in the opposite one, beyond the grid's
+    position range of all of them: ego 0 has no in-grid pair (U = +inf, every lower bound -inf)."""
+    ext = float(min(table.hi[0] - table.lo[0], table.hi[1] - table.lo[1]))
+    s = np.zeros((N, 4))
+    a, b = np.divmod(np.arange(N - 1), 8)
+    s[1:, 0], s[1:, 1] = -0.3 * ext + 0.05 * a, -0.3 * ext + 0.05 * b
+    s[0, 0] = s[0, 1] = 0.3 * ext
+    if dyn != "double_integrator":
+        s[:, 2] = 0.25 * np.arange(N)
+        s[:, 3] = 0.5 * (table.lo[3] + table.hi[3])
+    return s
+
+
+def arrive_subset(env, every=3):
+    """_arrive_all's recipe (tests/test_gpu_parity.py) for every ``every``-th agent of oracle env ``env``:
+    placed on its last goal at the goal's speed and heading with reached_goal = L - 1, so the next step
+    finishes it and done agents, egos and their candidates share a wave from then on."""
+    L, N = env.L, env.N
+    st, reached = env.s.copy(), np.asarray(env.reached_goal, dtype=np.int32).copy()
+    for i in range(0, N, every):
+        g = (L - 1) * N + i
+        sp, h = env.lm_speed[g], env.lm_heading[g]
+        st[i] = ([env.lm_pos[g][0], env.lm_pos[g][1], sp * np.cos(h), sp * np.sin(h)] if env.di else
+                 [env.lm_pos[g][0], env.lm_pos[g][1], h, sp])
+        reached[i] = L - 1
+    return st, reached
+
+
+def inject(oracle_env, states, reached=None):
+    """The oracle side of GpuGraphVecEnv.set_agent_state (as the existing injection tests do)."""
+    oracle_env.s[:] = states
+    if reached is not None:
+        oracle_env.reached_goal[:] = reached
+    oracle_env.calculate_distances()
+
+
+class _StateView:
+    """What pair_table reads of an oracle env, for a state that no env holds yet."""
+
+    def __init__(self, dyn, table, states):
+        from oracle.lsm_oracle import OracleEnv
+        self.di = dyn == "double_integrator"
+        self.s = np.asarray(states, dtype=np.float64)
+        self.N = self.s.shape[0]
+        self.done = np.zeros(self.N, dtype=bool)
+        self.departed = np.ones(self.N, dtype=bool)
+        self.hj_grid = Grid(table.lo, table.hi, table.shape, table.periodic)
+        self.values_hj = table.values_hj
+        self._rel_state = lambda e, o: OracleEnv._rel_state(self, e, o)
+        self._value = lambda rel: OracleEnv._value(self, rel)
+
+
+_SPIKE_CACHE = {}
+
+
+def spike_injections(dyn, table, bshift, N):
+    """The spike pairs' injected states for ``table`` (make_table(dyn, "spike", shape, bshift=bshift)):
+    per spike and side a dict(name, side, states, argmin, flips) with the crowd distance chosen as the
+    smallest of a fixed ladder at which the model says that partner 1 is ego 0's exact argmin and, for a
+    "below" pair, that mutant bounds prune it ("no_wrap" preferred for the wrap spike, else
+    "no_shared"). flips: mutant -> the argmin the pruned search would return with that mutant's bounds.
+    A ladder without such a rung returns the last rung; the caller's assertions then fail."""
+    key = (dyn, tuple(table.shape), bshift, N)
+    if key in _SPIKE_CACHE:
+        return _SPIKE_CACHE[key]
+    good = block_bounds(table.values_hj, table.periodic, bshift)
+    muts = {m: block_bounds(table.values_hj, table.periodic, bshift, mutant=m) for m in ("no_shared", "no_wrap")}
+    ext = float(table.hi[0])
+    out = []
+    for name, spike in spike_nodes(dyn, table.shape, bshift).items():
+        picked = {}
+        for want in (("no_wrap", "no_shared") if name == "wrap" else ("no_shared",)):
+            for cd in np.arange(1.2, ext - 0.35, 0.1):
+                view = _StateView(dyn, table, spike_layout(dyn, table, spike, "below", N, float(cd)))
+                pairs = pair_table(view, egos=[0])
+                st = prune_stats(view, table, bshift, bounds=good, pairs=pairs)
+                flips = {m: prune_stats(view, table, bshift, bounds=b, pairs=pairs)["pruned_argmin"][0]
+                         for m, b in muts.items()}
+                picked = dict(cd=float(cd), argmin=st["argmin"][0], pruned_argmin=st["pruned_argmin"][0], flips=flips)
+                if st["argmin"][0] == 1 and flips[want] != 1:
+                    break
+            else:
+                continue
+            break
+        for side in spike[2]:
+            states = spike_layout(dyn, table, spike, side, N, picked["cd"])
+            info = picked
+            if side != "below":
+                view = _StateView(dyn, table, states)
+                pairs = pair_table(view, egos=[0])
+                st = prune_stats(view, table, bshift, bounds=good, pairs=pairs)
+                info = dict(cd=picked["cd"], argmin=st["argmin"][0], pruned_argmin=st["pruned_argmin"][0],
+                            flips={m: prune_stats(view, table, bshift, bounds=b, pairs=pairs)["pruned_argmin"][0]
+                                   for m, b in muts.items()})
+            out.append(dict(name=name, side=side, states=states, **info))
+    _SPIKE_CACHE[key] = out
+    return out
