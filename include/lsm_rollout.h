@@ -278,9 +278,15 @@ int lsm_select_ring(lsm_env* env, int32_t index);
 int32_t lsm_action_errors(lsm_env* env, void* hip_stream);
 
 /* Name of the kernel instantiation lsm_step / lsm_reset launch for this handle (e.g.
- * "rollout_team_kernel<0, 8, 4>"), as rocprofv3 reports it without the namespace. Owned by the
- * library, valid until the next call on the same thread. */
+ * "rollout_team_kernel<0, 8, 4, false>"), as rocprofv3 reports it without the namespace. A constant
+ * owned by the library; "" for a handle whose creation failed. */
 const char* lsm_kernel_name(const lsm_env* env);
+
+/* The same answer without a handle or a device: the kernel lsm_create_select(cfg, select) would
+ * choose (select == NULL: the defaults, as in lsm_create). Returns 0 and writes the name into
+ * buf[cap], or 1 and writes the text lsm_last_error would give for the refused arguments (also 1 when
+ * cap is too small for the text, which is then cut). For tests of the selection rules. */
+int lsm_kernel_name_for(const lsm_config* cfg, const lsm_kernel_select* select, char* buf, size_t cap);
 
 /* Identity of this library's build: the first 16 hex digits of the sha256 of the step kernel's
  * sources and compiler flags (lsm.build), baked in at compile time. Profiles under profiles/

@@ -1,4 +1,8 @@
-// lsm_rollout.hip -- MI355X (gfx950) kernels + C ABI for the navigation_graph_safe rollout.
+// lsm_rollout.hip -- MI355X (gfx950) step kernels of the navigation_graph_safe rollout: the device
+// code of rollout_kernel (here), rollout_block_kernel (lsm_block.h) and rollout_team_kernel
+// (lsm_team.h), their launcher templates and, per build group (-DLSM_PART=g, lsm_kernels.h), the
+// launchers' explicit instantiations. The C ABI, the handle and the choice of a kernel are
+// lsm_host.hip's; both sides share lsm_params.h.
 //
 // One 64-lane wavefront (one workgroup) per environment. Everything an env needs for a
 // step -- agent states, landmarks, the E x E distance table, pairwise filter scratch and
@@ -35,18 +39,11 @@
 #include <vector>
 
 #include "../../include/lsm_rollout.h"
+#include "lsm_kernels.h"
 #include "lsm_numeric.h"
+#include "lsm_params.h"
 #include "lsm_rk45.h"
 #include "lsm_scenario.h"
-
-// Diagnostic switches (bounds that compute wrong results on purpose, in-kernel stamps) exist only in
-// variant builds (lsm.build.build_variants defines LSM_DIAGNOSTIC_BUILD); the product refuses them.
-#if !defined(LSM_DIAGNOSTIC_BUILD) &&                                                              \
-    (defined(LSM_STAMPS) || defined(LSM_XP_VALHOT) || defined(LSM_XP_GRADHOT) || defined(LSM_XP_NOFILT) || \
-     defined(LSM_XP_NOOUT) || defined(LSM_XP_NORESETEMIT) || defined(LSM_XP_NORK) || defined(LSM_XP_NOSCEN) || \
-     defined(LSM_XP_DELAY) || defined(LSM_XP_POISON))
-#error "diagnostic switch in a product build: use lsm.build.build_variants (LSM_DIAGNOSTIC_BUILD)"
-#endif
 
 // Diagnostic builds: LSM_XP_POISON=pattern sets every 32-bit word of a workgroup's dynamic LDS to the
 // pattern before the kernel's first LDS access. LDS is not cleared between workgroups, so a read of a
@@ -63,19 +60,6 @@
 #define LDS_POISON(base, bytes, tid, nthr) do { } while (0)
 #endif
 
-// LSM_PART (lsm.build): 0 = host code only, g > 0 = kernel group g only, undefined = everything
-#if defined(LSM_PART) && LSM_PART != 0
-#define LSM_HOST_PART 0
-#else
-#define LSM_HOST_PART 1
-#endif
-
-// stamps per env in LSM_OUT_DEBUG_STAMPS: 16 in the ABI; diagnostic builds stamp 40
-#ifdef LSM_STAMPS
-#define LSM_NSTAMP 40
-#else
-#define LSM_NSTAMP 16
-#endif
 #ifdef LSM_STAMPS
 // diagnostic build only: per-phase s_memtime stamps of each env's wave (never in the product .so)
 #define STAMP(k)                                                                             \
@@ -101,142 +85,6 @@
 
 namespace lsm {
 
-constexpr int WAVE = 64;
-constexpr int MAXN = 32;        // agents per env supported by the one-wave kernel
-constexpr int MAXE = 64;        // entities per env (N * (1 + L))
-constexpr int MT_WORDS = MT_N + 1;  // key[624] + pos
-constexpr int NCUR = 12;
-constexpr int NSTAT = 6;        // travel_length, travel_distance, done, conflict, min_distance, multiple
-constexpr int NWINFO = 4;       // times_required, dists_to_goal, dist_left_to_goal, num_agent_collisions
-// Per-env HJ separation history (record, after cur): HjDataHandle.update_separation_distance
-// (safety_filter.py:170-174) runs `values_hj -= shift` on every reset of every env, so each env's
-// table is the uploaded one minus its own chain of float64 shifts, each rounded to float32
-// (numpy: float32 array -= float64 scalar). sep[0] = number of shifts, sep[1] = the env's current
-// separation (sep[0] == 0: the uploaded table's, KParams::val_sep0), sep[2 + k] = shift k for
-// k < KSEP; longer chains continue in StateDev::sepx (HBM, grown by the host as the number of
-// separation changes since the upload grows), so no length is refused.
-constexpr int KSEP = 8;
-constexpr int NSEPW = 2 + KSEP;
-
-// HJ / TTR table in "cell-corner" layout: every grid cell stores the 2^ndim corner values
-// it interpolates (lexicographic corner order, dim 0 slowest) contiguously, so one query
-// reads 64 B (4-D) / 128 B (5-D) of values and 2^ndim * 16 * gw B of gradients -- one or
-// two cache lines instead of 2^ndim scattered nodes. 16x the node table (1.8 GB for the
-// full DI table): sized for 288 GB HBM, expanded on the device at upload.
-struct TableDev {
-  const float* cells;    // [n_cells][2^ndim]
-  const float4* gcells;  // [n_cells][2^ndim][gw]
-  int ndim;
-  int n[5];        // nodes per dim
-  int cstride[5];  // cell strides (cells per dim: n (periodic) or n - 1)
-  float lo[5];
-  float sp[5];
-  float rsp[5];    // 1 / sp (float32, correctly rounded)
-  int mdiv[5];     // 1: (s - lo) / sp by the reciprocal + one FMA correction (grid_pos), checked at
-                   // upload to equal the division bit for bit over every float32 the lookups can
-                   // meet (mdiv_check_kernel); 0: the division
-  int periodic[5];
-  int gw;  // float4 per corner gradient (1 for <= 4 dims, 2 for 5 dims)
-  // Value bounds per block of 2^bshift cells per dim: (min, max) of the block's nodes widened
-  // by the fp32 interpolation error (bounds_kernel). Small enough to stay in L2; the
-  // workgroup kernel uses them to skip exact lookups that cannot be the argmin. nullptr: none.
-  const float2* bnd;
-  int bshift;
-  int bstride[5];   // blocks: stride per dim
-};
-
-// Persistent per-env state: ONE contiguous record per env (env-major, 128-B aligned
-// stride) whose byte layout is exactly the head of the env's LDS block (lds_plan), so a
-// step starts with a straight float4 copy HBM -> LDS and ends with the copy back. Fields
-// (16-B aligned each), in record order:
-//   [0, a1)   ps [4][N], pdist, adiff [N] f64, done, reached, sfilt, decon [N] i32, step i32
-//   [a1, a2)  cur [NCUR] + the HJ shift chain                               (reset only)
-//   [a2, a3)  stats [NSTAT][N], winfo [NWINFO][N], gmt, minrel [N] f64
-//   [a3, rec) lm [6][NL] f64 (x, y, heading, speed, sin, cos), lmd            (reset only)
-// A step rewrites [0, a1) and [a2, a3). Everything a step needs before its distances is in
-// [0, a2) (state, done flags, curriculum, shifts): the team kernel loads that part first and
-// the rest while its agent wave filters and integrates (lsm_team.h).
-struct StateDev {
-  float4* rec;          // [n][rec_stride16]
-  uint32_t rec_stride16;
-  uint32_t rec16;       // float4 per record
-  uint32_t a1_16, a2_16, a3_16;   // the boundaries above, in float4
-  double* prev;         // [n][8] previous episode summary
-  uint32_t* mt;         // [n][MT_WORDS] (LSM_RNG_PHILOX: only word MT_N, the reset index + MT_N)
-  double* dep;          // [n][DEPW(N)] departed [N], departure_timer [N], init_theta [N], and the
-                        // final disconnect mask of the last call (u64 bits) (LSM_SCENARIO_DEPARTURES)
-  double* sepx;         // [n][sepx_cap] HJ separation shifts KSEP, KSEP + 1, ... of each env's chain
-  uint32_t sepx_cap;    // (nullptr / 0 until a chain can outgrow the record's KSEP slots)
-};
-
-struct OutDev {
-  float* obs;
-  float* node;
-  float* adj;
-  float* rew;
-  uint8_t* dones;
-  uint8_t* reset_flag;
-  double* ep_info;
-  double* info;
-  uint8_t* edges;
-  double* state;
-  uint64_t* adjmask;   // LSM_OUT_ADJ_MASK (compact adjacency layout)
-  float* share_obs;    // LSM_OUT_SHARE_OBS (optional)
-  float* masks;        // LSM_OUT_MASKS (optional)
-  float* active_masks; // LSM_OUT_ACTIVE_MASKS (optional)
-  double* cforce;      // LSM_OUT_COLLISION_FORCE (lsm_config.collision_forces only)
-  uint8_t* departed;   // LSM_OUT_DEPARTED (optional)
-  int64_t* adjnnz;     // LSM_OUT_ADJ_NNZ (optional): nonzeros of each ego's adjacency as stored
-};
-
-struct KParams {
-  int n_envs, N, L, NL, E, F, OBS, dyn, episode_length, use_masking, use_filter_arg, auto_reset;
-  int adj_compact;   // LSM_ADJ_COMPACT: unmasked E x E table once per env + per-ego masks
-  int lean;          // the team kernel carves the lean LDS layout (lds_plan)
-  int filter_search; // workgroup kernel's HJ argmin: 1 bound-pruned (default), 0 every pair exact
-  int scenario;      // LSM_SCENARIO_*
-  int rng;           // LSM_RNG_*
-  int nis;           // World.num_internal_step (>= 1): filter -> integrate repeats per step
-  int rbin;          // lsm_config.reward_terms (LSM_REWARD_* bits)
-  int collab;        // lsm_config.collaborative: shared reward
-  int rext;          // rbin || collab: rewards finished after every agent's goal / done update
-  int use_hj;        // the HJ handle exists (filter on, or LSM_REWARD_HJ_VALUE): resets shift it
-  int mt_stage;      // team-kernel resets: MT19937 words one lane may draw from the staged blocks
-                     // (2 MT_N; lsm_test_set_mt_stage lowers it so tests reach the cooperative redraw)
-  int64_t seed, env_offset;   // Philox keys: seed + 1000 * (env_offset + env)
-  uint32_t lds_dep_off;       // LSM_SCENARIO_DEPARTURES: LDS offset of the departure arrays
-  double dt, world_size, coord_range, world_eng, sep_target, max_speed, min_speed, gs_min, gs_max;
-  double coord_range_s;  // the largest double s with sqrt(s) <= coord_range (correctly rounded sqrt):
-                         // sqrt(s) > coord_range <=> s > coord_range_s, for squared distances s >= 0
-  double scen_d2lo, scen_d2hi;   // the scenario's separated-positions band (dmin, dmax) on squared
-                                 // distances: sqrt(s) > dmin <=> s > d2lo, sqrt(s) < dmax <=> s < d2hi
-  double act0[5], act1[5];
-  double mag_c[50], mag_s[50];
-  double cos_pi6, two_pi, pi;
-  double di_thr_xmax, di_thr_xmin, di_thr_ymax, di_thr_ymin, di_axmax, di_axmin, di_aymax, di_aymin;
-  double at_vmax, at_vmin, at_amax, at_amin, at_wmax, at_thr_amax, at_thr_amin;
-  float at_box_w, at_box_amax, at_box_amin;  // float32 box corners (jnp)
-  double ttr_max;
-  double val_sep0;       // separation of the uploaded value table (HjDataHandle.separation_distance)
-  uint32_t m_E, m_EE, m_EF, m_F, m_EF4, m_NL;  // ceil(2^32 / d) for exact small-numerator division
-  unsigned long long* stamps;     // LSM_OUT_DEBUG_STAMPS (diagnostic builds only)
-  int diag;                       // diagnostic builds: bit 0 skip adj/node stores, bit 1 skip filter (LSM_DIAG)
-  uint32_t lds_env_bytes;         // LDS bytes per env (envs per wave > 1: consecutive blocks)
-  const uint16_t* pairs;          // strict upper-triangle entity pairs (a | b << 8)
-  int32_t* action_err;            // set to 1 by a launch that saw an action index outside [0, 25)
-  TableDev val, ttr;
-  StateDev s;
-  OutDev o;
-};
-
-// Per-launch kernel arguments (the rest lives in a device-resident KParams per handle).
-struct KStep {
-  const void* actions;
-  const double* layout;   // mode 2: [n][layout doubles] (lsm_reset_layout)
-  int action_kind, mode, emit_edges, stop_after;   // mode 0 = step, 1 = reset all, 2 = reset from layout
-  double cur_new[NCUR];
-};
-
 // ----------------------------------------------------------------------------------
 // LDS layout (dynamic, 16-byte aligned carve). Two unions keep one env under ~9 KB at
 // N = 8 so LDS does not cap residency below the VGPR limit (16 waves / CU):
@@ -247,8 +95,6 @@ struct KStep {
 // (dead before the distances are computed), leaves U2 to the info rows and the node tables,
 // and drops fval's landmark-landmark block (its values are the episode's lmd cache).
 // ----------------------------------------------------------------------------------
-__host__ __device__ inline size_t align16_(size_t x) { return (x + 15) & ~(size_t)15; }
-
 struct Lds {
   // ---- persistent record (StateDev) ----
   double* ps;        // [4][N] agent state (after integration; velocities pre-freeze)
@@ -314,31 +160,8 @@ struct Lds {
   double* trig1;     // [4][N] cos, sin, vx, vy of the post state (node features)
 };
 
-// doubles per env of StateDev::dep: departed, timer, init_theta [N], then the accumulated
-// disconnect mask of the step's last ego (the next update_graph's), up to 4 words (E <= 256)
-__host__ __device__ inline int depw(int N) { return 3 * N + 4; }
-
-// LDS bytes of the departure arrays (appended after lds_plan's block)
-__host__ __device__ inline size_t dep_lds_bytes(int N) {
-  return 3 * align16_(4 * (size_t)N) + 3 * align16_(8 * (size_t)N) + align16_(32 * (size_t)N);
-}
-
-struct LdsPlan {
-  size_t bytes;     // LDS per env
-  size_t rec;       // persistent record bytes (LDS head == HBM record)
-  size_t a1, a2, a3;   // record sections (StateDev)
-  size_t off[40];
-};
-
-// Workgroup-per-env kernel (lsm_block.h): threads per env and its limits.
-constexpr int BT = 256;
-constexpr int BMAXN = 64;
-constexpr int BMAXE = 256;   // masks: E <= BT so one ballot per wave gives a mask word
-
 // q / d for q * d < 2^32 (all index math here): __umulhi(q, ceil(2^32 / d))
 __device__ __forceinline__ int fdiv(int q, uint32_t m) { return (int)__umulhi((uint32_t)q, m); }
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // Kernels are specialised on the agent count NT (L = 2, the training setting) so every
 // dimension, LDS offset and index division below folds to a constant; NT = 0 is the
@@ -403,105 +226,6 @@ __device__ __forceinline__ bool group_all(bool v) {
   const int g = (int)threadIdx.x / LPE;
   const uint64_t gm = (~0ull >> (64 - LPE)) << (g * LPE);
   return (b & gm) == gm;
-}
-
-// Offsets of every LDS array (shared by the host launch/record init and the device carve).
-// The record prefix (fields 0..14) is common to both kernels; the workgroup kernel keeps no
-// landmark-distance cache (lmd, 0 bytes), no E x E / N x N tables, and adds the entity
-// position table, per-ego multi-word masks and a node staging area.
-__host__ __device__ inline LdsPlan lds_plan(int N, int NL, int E, int F, bool block = false,
-                                            bool lean = false) {
-  LdsPlan p;
-  size_t o = 0;
-  int k = 0;
-  auto put = [&](size_t bytes) { p.off[k++] = o; o += align16(bytes); };
-  // record: fields 0..14 (carve order: ps stats winfo pdist gmt minrel adiff done reached sfilt
-  // decon step cur lm lmd) placed in the section order of StateDev
-  {
-    const size_t fsz[15] = {(size_t)8 * 4 * N, (size_t)8 * NSTAT * N, (size_t)8 * NWINFO * N, (size_t)8 * N,
-                            (size_t)8 * N, (size_t)8 * N, (size_t)8 * N, (size_t)4 * N, (size_t)4 * N,
-                            (size_t)4 * N, (size_t)4 * N, 8, (size_t)8 * (NCUR + NSEPW), (size_t)8 * 6 * NL,
-                            block ? 0 : (size_t)4 * (NL * (NL - 1) / 2)};
-    const int order[15] = {0, 3, 6, 7, 8, 9, 10, 11, 12, 1, 2, 4, 5, 13, 14};
-#pragma unroll
-    for (int q = 0; q < 15; ++q) {
-      const int f = order[q];
-      p.off[f] = o;
-      o += align16(fsz[f]);
-      if (f == 11) p.a1 = o;
-      if (f == 12) p.a2 = o;
-      if (f == 5) p.a3 = o;
-    }
-    k = 15;
-  }
-  p.rec = o;
-  const int MW = (E + 63) / 64;
-  // scratch
-  put(4 * N); put(4 * N); put(8 * 2 * N); put(8 * 2 * N); put(8 * 2 * N); put(8 * 2 * N);
-  put(block ? 8 * N * MW : 8 * N);
-  put(F == 10 ? 0 : 8 * 2 * N);
-  if (block) {
-    // fval aa aa2 -> none; U1 = {mt, scen, scratch} | {feat, egooff} | {pair partials, info rows}
-    put(8 * E); put(8 * E); put(4 * N); put(8 * 8);   // ex, ey, ccnt, mpre[4] + mpost[4]
-    const size_t u1 = o;
-    size_t c = align16(4 * MT_WORDS), d = c + align16(8 * SCEN_WS), e = d + align16(8 * 2 * N);
-    size_t g1 = F == 10 ? align16(8 * (2 * N + NL) * F) : align16(8 * 4 * N);
-    size_t g2 = g1 + (F == 10 ? align16(8 * N * F) : 0);
-    size_t m = 8 * 2 * BT;
-    m = m > (size_t)(8 * LSM_INFO_FIELDS * N) ? m : (size_t)(8 * LSM_INFO_FIELDS * N);
-    size_t u1sz = e > g2 ? e : g2;
-    u1sz = u1sz > align16(m) ? u1sz : align16(m);
-    // the filter's per-wave survivor queues (lsm_block.h): (i, j) u16 + value f32 per slot
-    const int tpe = (64 * N <= BT) ? 64 : (32 * N <= BT) ? 32 : (16 * N <= BT) ? 16 : (8 * N <= BT) ? 8 : 4;
-    const size_t qb = align16((size_t)(BT / WAVE) * WAVE * ((N + tpe - 1) / tpe) * 6);
-    u1sz = u1sz > qb ? u1sz : qb;
-    p.off[k++] = u1; p.off[k++] = u1 + c; p.off[k++] = u1 + d;   // mt, scen, scratch
-    p.off[k++] = u1; p.off[k++] = u1 + g1;                         // feat, egooff
-    p.off[k++] = u1;                                               // dpair: pair partials / info rows
-    o = u1 + u1sz;
-    // node staging (airtaxi, or DI with E * F % 4 != 0): live together with feat
-    const bool stage = F != 10 || ((E * F) & 3) != 0;
-    p.off[k++] = o;
-    o += stage ? align16(4 * BT * F) : 0;
-    p.bytes = o;
-    return p;
-  }
-  // U1
-  const size_t u1 = o;
-  const size_t fvb = lean ? (size_t)4 * (N * E + NL * N) : (size_t)4 * E * E;
-  size_t a = align16(fvb), a2 = a + align16(8 * N * N), b = a2 + align16(8 * N * N);
-  size_t c = align16(4 * MT_WORDS), d = c + align16(8 * SCEN_WS), e = d + align16(8 * 2 * MAXN);
-  p.off[k++] = u1; p.off[k++] = u1 + a; p.off[k++] = u1 + a2; p.off[k++] = u1; p.off[k++] = u1 + c;
-  p.off[k++] = u1 + d;
-  size_t u1sz = b > e ? b : e;
-  const size_t h0 = align16(4 * WAVE * F);   // node staging for up to 64 pairs
-  u1sz = u1sz > h0 ? u1sz : h0;
-  // pair matrices dpair, vpair, inr, then the team kernel's per-ego filter slots (filter_slot)
-  size_t f1 = align16(8 * N * N), f2 = f1 + align16(8 * N * N), f3 = f2 + align16(N * N) + align16(32 * N);
-  if (lean) u1sz = u1sz > f3 ? u1sz : f3;   // the pair matrices at the head of U1
-  o = u1 + u1sz;
-  // U2
-  const size_t u2 = o;
-  const size_t pb = lean ? u1 : u2;   // pair matrices
-  // DI entity rows + ego offsets; airtaxi: the [4][N] heading trig table (feat) only
-  size_t g1 = F == 10 ? align16(8 * (2 * N + NL) * F) : align16(8 * 4 * N);
-  size_t g2 = g1 + (F == 10 ? align16(8 * N * F) : 0);
-  p.off[k++] = pb; p.off[k++] = pb + f1; p.off[k++] = pb + f2;
-  p.off[k++] = u2; p.off[k++] = u2 + g1; p.off[k++] = u1;   // stage aliases U1 (adj emitted first)
-  size_t m = lean ? g2 : (f3 > g2 ? f3 : g2);
-  // magnetic partials + the segment constants (DI, filter off; team kernel: mag_table_store)
-  if (F == 10) m = m > (size_t)(8 * (2 * 64 + 100)) ? m : (size_t)(8 * (2 * 64 + 100));
-  m = m > (size_t)(8 * LSM_INFO_FIELDS * N) ? m : (size_t)(8 * LSM_INFO_FIELDS * N);   // info rows
-  // the next MT19937 block of a team-kernel reset (live with mt / scen; U2 is free then): after
-  // U1's scratch when it fits, else at the U2 base (the team kernels' layouts have room either way,
-  // lsm_create checks)
-  const size_t mtb = align16(4 * MT_N);
-  const bool mtn_u1 = u1sz - e >= mtb;
-  p.off[k++] = mtn_u1 ? u1 + e : u2;
-  if (!mtn_u1 && m < mtb) m = mtb;
-  o = u2 + m;
-  p.bytes = o;
-  return p;
 }
 
 __device__ __forceinline__ Lds carve(unsigned char* base, int N, int NL, int E, int F, bool lean = false) {
@@ -684,16 +408,6 @@ struct WaveRng {
 // Every dimension is computed without an early exit and the decision taken once at the end:
 // the table's per-dimension constants then load together instead of one scalar round trip per
 // dimension behind each exit (the latency-bound agent wave runs this in the filter).
-// The grid coordinate y / sp (y = s - lo in float32): the IEEE division, or -- where the upload check
-// found them equal for every float32 y the lookups can meet -- q = y r, q + (y - q sp) r with
-// r = 1 / sp (Markstein's correction, two FMAs instead of the ~10-instruction division sequence).
-__host__ __device__ __forceinline__ float grid_pos(float y, float sp, float rsp, int mdiv) {
-  if (!mdiv) return y / sp;
-  const float q = y * rsp;
-  const float r = fmaf(-q, sp, y);
-  return fmaf(r, rsp, q);
-}
-
 template <int ND>
 __device__ __forceinline__ bool grid_cell(const TableDev& T, const double* s, int& cell, float* w) {
   float lo[ND], sp[ND], rs[ND];
@@ -857,90 +571,6 @@ __device__ __forceinline__ bool value_bounds(const TableDev& T, const double* s,
   }
   return true;
 }
-
-#if LSM_HOST_PART
-// One thread per bounds block: min / max over the nodes its cells interpolate (cells
-// [b B, (b + 1) B) per dim -> nodes [b B, (b + 1) B] clipped, wrapped on periodic dims),
-// widened by 4e-6 max|v|: the fp32 sum of 2^d weighted corners stays within ~20 ulp of
-// max|v| of the exact convex combination, so an interpolated value never leaves the bounds.
-__global__ void bounds_kernel(const float* values, float2* bnd, TableDev T, int nblocks) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= nblocks) return;
-  const int B = 1 << T.bshift;
-  int lo[5], cnt[5];
-  int rem = b;
-  for (int d = T.ndim - 1; d >= 0; --d) {
-    const int ncell = T.periodic[d] ? T.n[d] : T.n[d] - 1;
-    const int nb = (ncell + B - 1) / B;
-    const int bd = rem % nb;
-    rem /= nb;
-    lo[d] = bd * B;
-    const int hi_cell = min(lo[d] + B, ncell);   // cells [lo, hi_cell)
-    cnt[d] = hi_cell - lo[d] + 1;                // nodes lo .. hi_cell
-  }
-  float mn = INFINITY, mx = -INFINITY;
-  int idx[5] = {0, 0, 0, 0, 0};
-  for (;;) {
-    int64_t node = 0;
-    for (int d = 0; d < T.ndim; ++d) {
-      int i = lo[d] + idx[d];
-      if (T.periodic[d] && i >= T.n[d]) i -= T.n[d];
-      node = node * T.n[d] + i;
-    }
-    const float v = values[node];
-    mn = fminf(mn, v);
-    mx = fmaxf(mx, v);
-    int d = T.ndim - 1;
-    while (d >= 0 && ++idx[d] == cnt[d]) idx[d--] = 0;
-    if (d < 0) break;
-  }
-  const float m = 4.0e-6f * fmaxf(fabsf(mn), fabsf(mx));
-  bnd[b] = make_float2(mn - m, mx + m);
-}
-#endif
-
-#if LSM_HOST_PART
-// grid_pos's reciprocal path against the division for every float32 y in [-neg, pos] (bit patterns
-// 0 .. pos_bits and the sign-flipped 0 .. neg_bits): bad = 1 on any difference (NaN == NaN).
-__global__ void mdiv_check_kernel(float sp, float rsp, uint32_t pos_bits, uint32_t neg_bits, int* bad) {
-  const uint64_t n = (uint64_t)pos_bits + 1 + (uint64_t)neg_bits + 1;
-  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const uint32_t b = i <= pos_bits ? (uint32_t)i : 0x80000000u | (uint32_t)(i - pos_bits - 1);
-    const float y = __uint_as_float(b);
-    const float a = grid_pos(y, sp, rsp, 0), c = grid_pos(y, sp, rsp, 1);
-    if (__float_as_uint(a) != __float_as_uint(c) && !(a != a && c != c)) *bad = 1;
-  }
-}
-#endif
-
-#if LSM_HOST_PART
-// Expand a node table into the cell-corner layout (one thread per (cell, corner)).
-__global__ void expand_cells_kernel(const float* values, const float4* grads, float* cells, float4* gcells,
-                                    TableDev T, int64_t n_cells) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int nc = 1 << T.ndim;
-  if (t >= n_cells * nc) return;
-  const int64_t cell = t / nc;
-  const int c = (int)(t - cell * nc);
-  int64_t rem = cell, node = 0, nstride = 1;
-  int idx[5];
-  for (int d = T.ndim - 1; d >= 0; --d) {
-    const int ncd = T.periodic[d] ? T.n[d] : T.n[d] - 1;
-    idx[d] = (int)(rem % ncd);
-    rem /= ncd;
-  }
-  for (int d = T.ndim - 1; d >= 0; --d) {
-    const int bit = (c >> (T.ndim - 1 - d)) & 1;
-    int i = idx[d] + bit;
-    if (T.periodic[d] && i >= T.n[d]) i -= T.n[d];
-    node += (int64_t)i * nstride;
-    nstride *= T.n[d];
-  }
-  cells[t] = values[node];
-  if (grads)
-    for (int q = 0; q < T.gw; ++q) gcells[t * T.gw + q] = grads[node * T.gw + q];
-}
-#endif
 
 // ----------------------------------------------------------------------------------
 // per-agent helpers
@@ -3448,1082 +3078,57 @@ __global__ __launch_bounds__(64, DYN == 0 ? (LPE == 64 ? 4 : 2) : LSM_WAVES_PER_
 #include "lsm_block.h"
 #include "lsm_team.h"
 
-#if LSM_HOST_PART
-// A new value table (a new HjDataHandle): every env's separation chain starts empty.
-__global__ void sep_clear_kernel(float4* rec, uint32_t rec_stride16, int n_envs, uint32_t sep_off) {
-  const int env = blockIdx.x * blockDim.x + threadIdx.x;
-  if (env >= n_envs) return;
-  double* sep = (double*)((unsigned char*)(rec + (size_t)env * rec_stride16) + sep_off);
-  sep[0] = 0.0;
-  sep[1] = 0.0;
-}
-#endif
-
-#if LSM_HOST_PART
-// env k's MT19937: np.random.seed(seed + 1000 * (env_offset + k))
-__global__ void seed_kernel(uint32_t* mt, int n_envs, int64_t seed, int64_t env_offset) {
-  const int env = blockIdx.x * blockDim.x + threadIdx.x;
-  if (env >= n_envs) return;
-  const uint32_t s = (uint32_t)(seed + 1000 * (env_offset + env));
-  uint32_t* key = mt + (size_t)env * MT_WORDS;
-  mt_seed(s, key, 1);
-  key[MT_N] = MT_N;
-}
-#endif
-
 }  // namespace lsm
 
-// ====================================================================================
-// C ABI
-// ====================================================================================
 using namespace lsm;
 
-struct lsm_env {
-  lsm_config cfg;
-  int mt_stage = 2 * MT_N;   // KParams::mt_stage (lsm_test_set_mt_stage)
-  uint16_t* pairs;
-  int N, L, NL, E, F, OBS;
-  StateDev s;
-  std::vector<void*> allocs;
-  void* out_ptr[LSM_NUM_OUT];
-  size_t out_bytes[LSM_NUM_OUT];
-  TableDev val, ttr;
-  double ttr_max;
-  double val_sep0;      // separation of the uploaded value table
-  double sep_last;      // separation of the last reset / step call (chain-length bound)
-  int sep_changes;      // changes of that separation since the table upload (>= any env's chain)
-  std::string err;
-  bool tables_ok;
-  int device;
-  KParams* dparams;   // device copy of the per-handle constants (re-uploaded when dirty)
-  int32_t* action_err;   // device flag: an action index outside [0, 25) since the last check
-  bool params_dirty;
-  // ring-bound output slots (lsm_bind_output_ring): ring index i writes slot s at
-  // ring_base[s] + (i + ring_off[s]) * ring_stride[s] when that lands in [0, ring_count[s]),
-  // else at out_ptr[s]. One KParams copy per ring index lives in dring; selecting an index is a
-  // host-side pointer choice (no upload, no sync per step).
-  void* ring_base[LSM_NUM_OUT];
-  size_t ring_stride[LSM_NUM_OUT];
-  int32_t ring_count[LSM_NUM_OUT], ring_off[LSM_NUM_OUT];
-  int32_t ring_len;    // number of ring indices (0: no ring slots)
-  int32_t ring_cap;    // KParams copies allocated in dring
-  int32_t ring_sel;    // -1: plain bindings
-  KParams* dring;
-  lsm_kernel_select sel;   // lsm_create_select's kernel choice (tests, A/B runs)
-  int lpe;   // lanes per env: 64 (one env per wave), 32 or 16 (2 or 4 envs per wave)
-  bool block;   // workgroup-per-env kernel (N > 32 or E > 64, or sel.workgroup_per_env)
-  bool generic_only;   // sel.generic: never use the compile-time-N kernels (tests)
-  int team;   // envs per workgroup of the team kernel (lsm_team.h); 0 = rollout_kernel
-  bool lean;  // the team kernel's lean LDS layout (airtaxi, N % 4 == 0, E % 4 == 0)
-};
-
-static int fail(lsm_env* e, const std::string& msg) {
-  if (e) e->err = msg;
-  return 1;
-}
-
-// the reference builds an HjDataHandle (use_hj_handle, navigation_graph_safe.py:195)
-static bool uses_hj(const lsm_env* e) {
-  return e->cfg.use_safety_filter || (e->cfg.reward_terms & LSM_REWARD_HJ_VALUE);
-}
-
-#define HIPCHK(env, expr)                                                              \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess) return fail(env, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-template <class T>
-static int dalloc(lsm_env* e, T** p, size_t count) {
-  void* q = nullptr;
-  hipError_t r = hipMalloc(&q, count * sizeof(T) + 16);
-  if (r != hipSuccess) return fail(e, std::string("hipMalloc: ") + hipGetErrorString(r));
-  e->allocs.push_back(q);
-  *p = (T*)q;
+// ---- launchers (lsm_kernels.h: one function type for every kernel) ------------------------------
+template <int DYN, int LPE, int NT>
+int launch_t(const KParams* P, int num_envs, const KStep& L, size_t env_lds, hipStream_t st) {
+  constexpr int G = WAVE / LPE;
+  const int blocks = (num_envs + G - 1) / G;
+  hipLaunchKernelGGL((rollout_kernel<DYN, LPE, NT>), dim3(blocks), dim3(WAVE), env_lds * G, st, P, L);
   return 0;
 }
 
-static const KParams* active_params(const lsm_env* e) {
-  return e->ring_sel >= 0 ? (const KParams*)(e->dring + e->ring_sel) : (const KParams*)e->dparams;
-}
-
-template <int DYN, int LPE, int NT>
-void launch_t(lsm_env* e, const KStep& L, size_t env_lds, hipStream_t st) {
-  constexpr int G = WAVE / LPE;
-  const int blocks = (e->cfg.num_envs + G - 1) / G;
-  hipLaunchKernelGGL((rollout_kernel<DYN, LPE, NT>), dim3(blocks), dim3(WAVE), env_lds * G, st,
-                     active_params(e), L);
-}
-
 template <int DYN, int NT, int G, bool REXT>
-int launch_team_t(lsm_env* e, const KStep& L, size_t env_bytes, hipStream_t st) {
+int launch_team_t(const KParams* P, int num_envs, const KStep& L, size_t env_bytes, hipStream_t st) {
   static bool attr = false;   // LDS above the 64 KB default needs an explicit opt-in
 #ifndef LSM_AB_LDS_PAD   // A/B variant builds only: extra LDS per workgroup (fewer workgroups per CU)
 #define LSM_AB_LDS_PAD 0
 #endif
   const size_t lds = env_bytes * G + LSM_AB_LDS_PAD;
   if (!attr && lds > 65536) {
-    HIPCHK(e, hipFuncSetAttribute((const void*)rollout_team_kernel<DYN, NT, G, REXT>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const hipError_t r = hipFuncSetAttribute((const void*)rollout_team_kernel<DYN, NT, G, REXT>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (r != hipSuccess) return (int)r;
     attr = true;
   }
-  const int blocks = (e->cfg.num_envs + G - 1) / G;
-  hipLaunchKernelGGL((rollout_team_kernel<DYN, NT, G, REXT>), dim3(blocks), dim3(WAVE * G), lds, st,
-                     active_params(e), L);
+  const int blocks = (num_envs + G - 1) / G;
+  hipLaunchKernelGGL((rollout_team_kernel<DYN, NT, G, REXT>), dim3(blocks), dim3(WAVE * G), lds, st, P, L);
   return 0;
 }
 
 template <int DYN, int NT, bool NIS1, bool REXT>
-int launch_block_nis(lsm_env* e, const KStep& L, size_t env_lds, hipStream_t st) {
+int launch_block_t(const KParams* P, int num_envs, const KStep& L, size_t env_lds, hipStream_t st) {
   static bool attr = false;   // LDS above the 64 KB default needs an explicit opt-in
   if (!attr && env_lds > 65536) {
-    HIPCHK(e, hipFuncSetAttribute((const void*)rollout_block_kernel<DYN, NT, NIS1, REXT>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)env_lds));
+    const hipError_t r = hipFuncSetAttribute((const void*)rollout_block_kernel<DYN, NT, NIS1, REXT>,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)env_lds);
+    if (r != hipSuccess) return (int)r;
     attr = true;
   }
-  hipLaunchKernelGGL((rollout_block_kernel<DYN, NT, NIS1, REXT>), dim3(e->cfg.num_envs), dim3(BT), env_lds, st,
-                     active_params(e), L);
+  hipLaunchKernelGGL((rollout_block_kernel<DYN, NT, NIS1, REXT>), dim3(num_envs), dim3(BT), env_lds, st, P, L);
   return 0;
 }
 
-template <int DYN, int NT>
-int launch_block_t(lsm_env* e, const KStep& L, size_t env_lds, hipStream_t st) {
-  if (e->cfg.num_internal_step > 1) return launch_block_nis<DYN, NT, false, true>(e, L, env_lds, st);
-  // fill_params' P.rext: reward_finish / reward_shared run only then
-  const bool rext = e->cfg.reward_terms != 0 || e->cfg.collaborative;
-  return rext ? launch_block_nis<DYN, NT, true, true>(e, L, env_lds, st)
-              : launch_block_nis<DYN, NT, true, false>(e, L, env_lds, st);
-}
-
-
-// ---- kernel groups ------------------------------------------------------------------------
-// lsm.build compiles this file once per group (-DLSM_PART=g, in parallel) plus once for the host
-// code (-DLSM_PART=0, which declares every group's launchers extern); without LSM_PART everything
-// is one translation unit (diagnostic builds).
-#define LSM_G1(X) X(0, 64, 0) X(0, 32, 0) X(0, 16, 0) X(0, 32, 8) X(0, 64, 3) X(0, 64, 8)
-#define LSM_G2(X) X(1, 64, 0) X(1, 32, 0) X(1, 16, 0) X(1, 32, 16) X(1, 64, 3) X(1, 64, 16)
-#define LSM_G3(X) X(0, 8, 8, false) X(0, 8, 4, false) X(0, 8, 2, false)
-#define LSM_G4(X) X(1, 16, 4, false) X(1, 16, 2, false)
-#define LSM_G7(X) X(0, 8, 8, true) X(0, 8, 4, true) X(0, 8, 2, true)
-#define LSM_G8(X) X(1, 16, 4, true) X(1, 16, 2, true)
-#define LSM_G5(X) X(0, 64) X(0, 0)
-#define LSM_G6(X) X(1, 64) X(1, 0)
-#define LSM_RT(a, b, c) template void launch_t<a, b, c>(lsm_env*, const KStep&, size_t, hipStream_t);
-#define LSM_TT(a, b, c, r) template int launch_team_t<a, b, c, r>(lsm_env*, const KStep&, size_t, hipStream_t);
-#define LSM_BK(a, b) template int launch_block_t<a, b>(lsm_env*, const KStep&, size_t, hipStream_t);
-#define LSM_RT_E(a, b, c) extern LSM_RT(a, b, c)
-#define LSM_TT_E(a, b, c, r) extern LSM_TT(a, b, c, r)
-#define LSM_BK_E(a, b) extern LSM_BK(a, b)
-#if defined(LSM_PART) && LSM_PART == 0
-LSM_G1(LSM_RT_E) LSM_G2(LSM_RT_E) LSM_G3(LSM_TT_E) LSM_G4(LSM_TT_E) LSM_G5(LSM_BK_E) LSM_G6(LSM_BK_E)
-LSM_G7(LSM_TT_E) LSM_G8(LSM_TT_E)
-#elif defined(LSM_PART) && LSM_PART == 1
-LSM_G1(LSM_RT)
-#elif defined(LSM_PART) && LSM_PART == 2
-LSM_G2(LSM_RT)
-#elif defined(LSM_PART) && LSM_PART == 3
-LSM_G3(LSM_TT)
-#elif defined(LSM_PART) && LSM_PART == 4
-LSM_G4(LSM_TT)
-#elif defined(LSM_PART) && LSM_PART == 5
-LSM_G5(LSM_BK)
-#elif defined(LSM_PART) && LSM_PART == 6
-LSM_G6(LSM_BK)
-#elif defined(LSM_PART) && LSM_PART == 7
-LSM_G7(LSM_TT)
-#elif defined(LSM_PART) && LSM_PART == 8
-LSM_G8(LSM_TT)
+// ---- this build group's instantiations (lsm.build: -DLSM_PART=1..8) -----------------------------
+#ifndef LSM_PART
+#error "lsm_rollout.hip is compiled once per kernel group: -DLSM_PART=1..8 (lsm_kernels.h, lsm.build)"
 #endif
-
-#if LSM_HOST_PART
-
-static void fill_params(const lsm_env* e, KParams& P) {
-  memset(&P, 0, sizeof(P));
-  const bool di = e->cfg.dynamics == LSM_DOUBLE_INTEGRATOR;
-  P.n_envs = e->cfg.num_envs;
-  P.N = e->N; P.L = e->L; P.NL = e->NL; P.E = e->E; P.F = e->F; P.OBS = e->OBS;
-  P.dyn = di ? 0 : 1;
-  P.episode_length = e->cfg.episode_length;
-  P.use_masking = e->cfg.use_masking;
-  P.use_filter_arg = e->cfg.use_safety_filter;
-  P.auto_reset = e->cfg.auto_reset;
-  P.adj_compact = e->cfg.adj_layout == LSM_ADJ_COMPACT;
-  P.filter_search = e->sel.filter_search == 0 ? 0 : 1;
-  P.scenario = e->cfg.scenario;
-  P.rng = e->cfg.rng;
-  P.nis = e->cfg.num_internal_step > 1 ? e->cfg.num_internal_step : 1;
-  P.rbin = e->cfg.reward_terms;
-  P.collab = e->cfg.collaborative ? 1 : 0;
-  P.rext = (P.rbin != 0 || P.collab) ? 1 : 0;
-  P.use_hj = (e->cfg.use_safety_filter || (e->cfg.reward_terms & LSM_REWARD_HJ_VALUE)) ? 1 : 0;
-  P.mt_stage = e->mt_stage;
-  P.seed = e->cfg.seed;
-  P.env_offset = e->cfg.env_offset;
-  P.lds_dep_off = (uint32_t)lds_plan(e->N, e->NL, e->E, e->F, e->block).bytes;
-  P.lean = e->lean ? 1 : 0;
-  P.world_size = e->cfg.world_size;
-  const double pi = 3.141592653589793;
-  P.pi = pi;
-  P.two_pi = 2 * pi;
-  if (di) {
-    P.dt = 0.1; P.coord_range = 4; P.world_eng = 1.0; P.sep_target = 0.5;
-    P.max_speed = 0.5; P.min_speed = 0.0; P.gs_min = 0.1; P.gs_max = 0.5;
-    const double opts[5] = {-0.5, -0.25, 0.0, 0.25, 0.5};   // np.linspace(-0.5, 0.5, 5)
-    for (int k = 0; k < 5; ++k) { P.act0[k] = opts[k]; P.act1[k] = opts[k]; }
-  } else {
-    P.dt = 1.0; P.coord_range = 3 * 1.60934; P.world_eng = 1.4; P.sep_target = 1500 * 0.0003048;
-    P.max_speed = 175 * 0.514444 * 0.001; P.min_speed = 60 * 0.514444 * 0.001;
-    P.gs_min = 60 * 0.514444 * 0.001; P.gs_max = 110 * 0.514444 * 0.001;
-    // np.linspace(-0.1, 0.1, 5), np.linspace(-0.001, 0.002, 5)
-    const double lo = -0.1, hi = 0.1, alo = -0.001, ahi = 0.002;
-    for (int k = 0; k < 5; ++k) {
-      P.act0[k] = (k == 4) ? hi : lo + k * ((hi - lo) / 4);
-      P.act1[k] = (k == 4) ? ahi : alo + k * ((ahi - alo) / 4);
-    }
-  }
-  {
-    double t = P.coord_range * P.coord_range;
-    while (std::sqrt(t) > P.coord_range) t = std::nextafter(t, 0.0);
-    while (std::sqrt(std::nextafter(t, INFINITY)) <= P.coord_range) t = std::nextafter(t, INFINITY);
-    P.coord_range_s = t;
-  }
-  {   // random_scenario_wave2's band, the device's products (lsm_team.h)
-    const double dmin = di ? 0.25 * P.coord_range : 0.5 * P.coord_range;
-    const double dmax = di ? 0.75 * P.coord_range : P.coord_range;
-    double lo = dmin * dmin;
-    while (std::sqrt(lo) > dmin) lo = std::nextafter(lo, 0.0);
-    while (std::sqrt(std::nextafter(lo, INFINITY)) <= dmin) lo = std::nextafter(lo, INFINITY);
-    double hi = dmax * dmax;
-    while (std::sqrt(hi) < dmax) hi = std::nextafter(hi, INFINITY);
-    while (std::sqrt(std::nextafter(hi, 0.0)) >= dmax) hi = std::nextafter(hi, 0.0);
-    P.scen_d2lo = lo;
-    P.scen_d2hi = hi;
-  }
-  P.cos_pi6 = cos(pi / 6);
-  for (int k = 0; k < 50; ++k) {
-    const double ph = k * ((2 * pi - 0) / 50);   // np.linspace(0, 2pi, 50, endpoint=False)
-    P.mag_c[k] = cos(ph);
-    P.mag_s[k] = sin(ph);
-  }
-  P.di_thr_xmax = 0.5 - 0.1 * 0.5; P.di_thr_xmin = -0.5 - 0.1 * -0.5;
-  P.di_thr_ymax = 0.5 - 0.1 * 0.5; P.di_thr_ymin = -0.5 - 0.1 * -0.5;
-  P.di_axmax = 0.5; P.di_axmin = -0.5; P.di_aymax = 0.5; P.di_aymin = -0.5;
-  P.at_vmax = 175 * 0.514444 * 0.001; P.at_vmin = 60 * 0.514444 * 0.001;
-  P.at_amax = 0.002; P.at_amin = -0.001; P.at_wmax = 0.1;
-  P.at_thr_amax = P.at_vmax - 1.0 * 0.002; P.at_thr_amin = P.at_vmin - 1.0 * -0.001;
-  P.at_box_w = (float)0.1; P.at_box_amax = (float)0.002; P.at_box_amin = (float)-0.001;
-  auto magic = [](uint32_t d) { return (uint32_t)((((uint64_t)1 << 32) + d - 1) / d); };
-  P.m_E = magic(e->E);
-  P.m_EE = magic(e->E * e->E);
-  P.m_EF = magic(e->E * e->F);
-  P.m_F = magic(e->F);
-  P.m_EF4 = magic(e->E * e->F / 4);
-  P.m_NL = magic(e->NL);
-  P.ttr_max = e->ttr_max;
-  P.val_sep0 = e->val_sep0;
-  P.val = e->val;
-  P.ttr = e->ttr;
-  P.s = e->s;
-  P.o.obs = (float*)e->out_ptr[LSM_OUT_OBS];
-  P.o.node = (float*)e->out_ptr[LSM_OUT_NODE_OBS];
-  P.o.adj = (float*)e->out_ptr[LSM_OUT_ADJ];
-  P.o.rew = (float*)e->out_ptr[LSM_OUT_REWARD];
-  P.o.dones = (uint8_t*)e->out_ptr[LSM_OUT_DONE];
-  P.o.reset_flag = (uint8_t*)e->out_ptr[LSM_OUT_RESET_FLAG];
-  P.o.ep_info = (double*)e->out_ptr[LSM_OUT_EP_INFO];
-  P.o.info = (double*)e->out_ptr[LSM_OUT_INFO];
-  P.o.edges = (uint8_t*)e->out_ptr[LSM_OUT_EDGES];
-  P.o.state = (double*)e->out_ptr[LSM_OUT_STATE];
-  P.o.adjmask = (uint64_t*)e->out_ptr[LSM_OUT_ADJ_MASK];
-  P.o.share_obs = (float*)e->out_ptr[LSM_OUT_SHARE_OBS];
-  P.o.masks = (float*)e->out_ptr[LSM_OUT_MASKS];
-  P.o.active_masks = (float*)e->out_ptr[LSM_OUT_ACTIVE_MASKS];
-  P.o.cforce = e->cfg.collision_forces ? (double*)e->out_ptr[LSM_OUT_COLLISION_FORCE] : nullptr;
-  P.o.departed = (uint8_t*)e->out_ptr[LSM_OUT_DEPARTED];
-  P.o.adjnnz = (int64_t*)e->out_ptr[LSM_OUT_ADJ_NNZ];
-  P.stamps = (unsigned long long*)e->out_ptr[LSM_OUT_DEBUG_STAMPS];
-  P.diag = 0;
-#ifdef LSM_STAMPS
-  if (const char* v = getenv("LSM_DIAG")) P.diag = atoi(v);
-#endif
-  P.pairs = e->pairs;
-  P.action_err = e->action_err;
-}
-
-extern "C" {
-
-size_t lsm_output_bytes(const lsm_env* e, int32_t slot) {
-  const size_t n = e->cfg.num_envs, N = e->N, E = e->E;
-  switch (slot) {
-    case LSM_OUT_OBS: return n * N * e->OBS * 4;
-    case LSM_OUT_NODE_OBS: return n * N * E * e->F * 4;
-    case LSM_OUT_ADJ: return (e->cfg.adj_layout == LSM_ADJ_COMPACT ? n : n * N) * E * E * 4;
-    case LSM_OUT_ADJ_MASK: return n * N * ((E + 63) / 64) * 8;
-    case LSM_OUT_REWARD: return n * N * 4;
-    case LSM_OUT_DONE: return n * N;
-    case LSM_OUT_RESET_FLAG: return n;
-    case LSM_OUT_EP_INFO: return n * 8 * 8;
-    case LSM_OUT_INFO: return n * N * LSM_INFO_FIELDS * 8;
-    case LSM_OUT_EDGES: return n * E * E;
-    case LSM_OUT_STATE: return n * N * 4 * 8;
-    case LSM_OUT_DEBUG_STAMPS: return n * LSM_NSTAMP * 8;
-    case LSM_OUT_SHARE_OBS: return n * N * N * e->OBS * 4;
-    case LSM_OUT_MASKS: return n * N * 4;
-    case LSM_OUT_ACTIVE_MASKS: return n * N * 4;
-    case LSM_OUT_COLLISION_FORCE: return n * N * 2 * 8;
-    case LSM_OUT_DEPARTED: return n * N;
-    case LSM_OUT_ADJ_NNZ: return n * N * 8;
-    default: return 0;
-  }
-}
-
-int32_t lsm_num_entities(const lsm_env* e) { return e->E; }
-int32_t lsm_layout_doubles(const lsm_env* e) {
-  return e ? 4 * e->N + 4 * e->NL + (e->cfg.scenario == LSM_SCENARIO_DEPARTURES ? 3 * e->N : 0) + 1 : 0;
-}
-int32_t lsm_node_features(const lsm_env* e) { return e->F; }
-int32_t lsm_obs_dim(const lsm_env* e) { return e->OBS; }
-const char* lsm_last_error(const lsm_env* e) { return e ? e->err.c_str() : "null handle"; }
-
-int lsm_create(const lsm_config* cfg, lsm_env** out) { return lsm_create_select(cfg, nullptr, out); }
-
-int lsm_create_select(const lsm_config* cfg, const lsm_kernel_select* sel, lsm_env** out) {
-  *out = nullptr;
-  if (!cfg) return 1;
-  lsm_env* e = new lsm_env();
-  *out = e;
-  e->cfg = *cfg;
-  if (sel) {
-    e->sel = *sel;
-  } else {
-    memset(&e->sel, 0, sizeof(e->sel));
-    e->sel.team = -1;
-    e->sel.lean = -1;
-    e->sel.filter_search = -1;
-  }
-  {
-    const lsm_kernel_select& s = e->sel;
-    if (s.workgroup_per_env != 0 && s.workgroup_per_env != 1) return fail(e, "kernel select: workgroup_per_env must be 0 or 1");
-    if (s.generic != 0 && s.generic != 1) return fail(e, "kernel select: generic must be 0 or 1");
-    if (s.lanes_per_env != 0 && s.lanes_per_env != 16 && s.lanes_per_env != 32 && s.lanes_per_env != 64)
-      return fail(e, "kernel select: lanes_per_env must be 0, 16, 32 or 64");
-    if (s.team != -1 && s.team != 0 && s.team != 2 && s.team != 4 && s.team != 8)
-      return fail(e, "kernel select: team must be -1, 0, 2, 4 or 8");
-    if (s.lean < -1 || s.lean > 1) return fail(e, "kernel select: lean must be -1, 0 or 1");
-    if (s.filter_search < -1 || s.filter_search > 1) return fail(e, "kernel select: filter_search must be -1, 0 or 1");
-    if (s.bounds_shift < 0 || s.bounds_shift > 4) return fail(e, "kernel select: bounds_shift must be in [0, 4]");
-  }
-  e->tables_ok = false;
-  e->dparams = nullptr;
-  for (int k = 0; k < LSM_NUM_OUT; ++k) {
-    e->ring_base[k] = nullptr; e->ring_stride[k] = 0; e->ring_count[k] = 0; e->ring_off[k] = 0;
-  }
-  e->ring_len = 0; e->ring_cap = 0; e->ring_sel = -1; e->dring = nullptr;
-  e->params_dirty = true;
-  e->ttr_max = 0.0;
-  e->val_sep0 = e->sep_last = 0.0;
-  e->sep_changes = 0;
-  memset(&e->val, 0, sizeof(e->val));
-  memset(&e->ttr, 0, sizeof(e->ttr));
-  for (int k = 0; k < LSM_NUM_OUT; ++k) { e->out_ptr[k] = nullptr; e->out_bytes[k] = 0; }
-  const int N = cfg->num_agents, L = cfg->num_landmarks;
-  if (cfg->dynamics != LSM_DOUBLE_INTEGRATOR && cfg->dynamics != LSM_AIRTAXI)
-    return fail(e, "dynamics must be LSM_DOUBLE_INTEGRATOR or LSM_AIRTAXI");
-  if (N < 2 || N > BMAXN) return fail(e, "num_agents must be in [2, 64]");
-  if (L < (cfg->scenario == LSM_SCENARIO_TRAIN ? 2 : 1) || L > MAX_L)
-    return fail(e, "num_landmarks must be in [2, 8] (the training scenario asserts > 1, utils.py:31; "
-                   "layout scenarios: [1, 8])");
-  if (N * (1 + L) > BMAXE) return fail(e, "N * (1 + L) must be <= 256");
-  if (N * L - 1 > 127) return fail(e, "landmark ids go through np.int8 (navigation_graph_safe.py:581)");
-  if (cfg->adj_layout != LSM_ADJ_REFERENCE && cfg->adj_layout != LSM_ADJ_COMPACT)
-    return fail(e, "adj_layout must be LSM_ADJ_REFERENCE or LSM_ADJ_COMPACT");
-  if (cfg->scenario < LSM_SCENARIO_TRAIN || cfg->scenario > LSM_SCENARIO_DEPARTURES)
-    return fail(e, "scenario must be LSM_SCENARIO_TRAIN, _LAYOUT or _DEPARTURES");
-  if (cfg->rng != LSM_RNG_MT19937 && cfg->rng != LSM_RNG_PHILOX)
-    return fail(e, "rng must be LSM_RNG_MT19937 or LSM_RNG_PHILOX");
-  if (cfg->scenario != LSM_SCENARIO_TRAIN) {
-    if (cfg->auto_reset)
-      return fail(e, "layout scenarios are evaluation paths (GraphDummyVecEnv, scripts/eval_mpe.py): auto_reset must be 0");
-    if (cfg->rng != LSM_RNG_MT19937) return fail(e, "layout scenarios draw on the host: rng must be LSM_RNG_MT19937");
-  }
-  if (cfg->scenario == LSM_SCENARIO_DEPARTURES && cfg->dynamics != LSM_AIRTAXI)
-    return fail(e, "departure timers need airtaxi dynamics (RealisticScenario calls "
-                   "reset_velocity(theta, speed), KinematicVehicleXYState only, core.py:137)");
-  e->block = N > MAXN || N * (1 + L) > MAXE || e->sel.workgroup_per_env == 1;
-  if (cfg->num_envs < 1) return fail(e, "num_envs must be >= 1");
-  if (cfg->num_internal_step < 0 || cfg->num_internal_step > 64)
-    return fail(e, "num_internal_step must be in [0, 64] (0 and 1: one inner step)");
-  if (cfg->episode_length < 1) return fail(e, "episode_length must be >= 1");
-  if (cfg->reward_terms & ~LSM_REWARD_ALL)
-    return fail(e, "reward_terms: unknown LSM_REWARD_* bits (RewardBinaryConfig has four optional terms, "
-                   "multiagent/config.py:78-83)");
-  if (cfg->collaborative != 0 && cfg->collaborative != 1) return fail(e, "collaborative must be 0 or 1");
-  e->N = N; e->L = L; e->NL = N * L; e->E = N * (1 + L);
-  e->F = cfg->dynamics == LSM_DOUBLE_INTEGRATOR ? 10 : 11;
-  e->OBS = cfg->dynamics == LSM_DOUBLE_INTEGRATOR ? 7 : 6;
-  // Lanes per env: 64 = one env per wave (default; measured fastest at 4096 envs, where
-  // 4 waves/SIMD hide LDS/HBM latency), 32/16 = 2/4 envs per wave sharing the per-agent
-  // instruction stream (needs N <= lanes). sel.lanes_per_env overrides.
-  e->lpe = e->sel.lanes_per_env ? e->sel.lanes_per_env : 64;
-  e->generic_only = e->sel.generic == 1;
-  if (e->block) e->lpe = 64;   // lanes_per_env applies to the one-wave kernel only
-  if (cfg->scenario != LSM_SCENARIO_TRAIN) {   // layouts: the generic one-wave kernel (mode 2 resets)
-    e->generic_only = true;
-    e->lpe = 64;
-  }
-  // Team kernel (lsm_team.h) for the compile-time-N BASELINE agent counts: G envs per
-  // workgroup share one wave for their per-agent phases. sel.team = 0 selects rollout_kernel,
-  // sel.team = G another instantiated G.
-  e->team = 0;
-  // the team kernel runs World.step's inner loop once (num_internal_step = 1, the training
-  // default, train.sh:35); more inner steps run in rollout_kernel / the workgroup kernel
-  if (!e->block && e->lpe == 64 && L == 2 && !e->generic_only && cfg->num_internal_step <= 1) {
-    if (cfg->dynamics == LSM_DOUBLE_INTEGRATOR && N == 8) e->team = 4;   // measured: 4 < 8 < 2 (us/step)
-    if (cfg->dynamics == LSM_AIRTAXI && N == 16) e->team = 4;   // lean LDS: 4 < 2 < 0 (us/step)
-    const int g = e->sel.team;
-    if (g == 0) e->team = 0;
-    else if (g > 0 && e->team && g * N <= 64) e->team = g;
-    else if (g > 0 && e->team) return fail(e, "kernel select: team * num_agents must be <= 64");
-  }
-  // an explicit team size is honoured or refused: a parity test that asked for the team kernel
-  // and got rollout_kernel would pass without running it
-  if (e->sel.team > 0 && e->team != e->sel.team)
-    return fail(e, "kernel select: team > 0 needs a team kernel instantiation (double integrator N = 8 or "
-                   "airtaxi N = 16, 2 landmarks, lanes_per_env 64, num_internal_step <= 1, the training "
-                   "scenario, neither generic nor workgroup_per_env)");
-  // lean LDS layout for the airtaxi team kernel (6 -> 8 envs per CU at N = 16);
-  // sel.lean = 0 keeps the full table (A/B)
-  e->lean = e->team && cfg->dynamics == LSM_AIRTAXI && (N & 3) == 0 && (e->E & 3) == 0;
-  if (e->sel.lean == 0) e->lean = false;
-  if (!(e->lpe == 16 || e->lpe == 32 || e->lpe == 64) || e->lpe < (e->block ? 1 : N))
-    return fail(e, "kernel select: lanes_per_env must be 16, 32 or 64 and >= num_agents");
-  HIPCHK(e, hipGetDevice(&e->device));
-  const size_t n = cfg->num_envs;
-  int r = 0;
-  const LdsPlan lp = lds_plan(N, e->NL, e->E, e->F, e->block);
-  e->s.rec16 = (uint32_t)(lp.rec / 16);
-  e->s.a1_16 = (uint32_t)(lp.a1 / 16);
-  e->s.a2_16 = (uint32_t)(lp.a2 / 16);
-  e->s.a3_16 = (uint32_t)(lp.a3 / 16);
-  e->s.rec_stride16 = (uint32_t)(((lp.rec + 127) / 128) * 8);   // 128-B aligned records
-  r |= dalloc(e, &e->s.rec, n * e->s.rec_stride16);
-  r |= dalloc(e, &e->s.prev, n * 8);
-  r |= dalloc(e, &e->dparams, 1);
-  r |= dalloc(e, &e->s.mt, n * MT_WORDS);
-  r |= dalloc(e, &e->pairs, (size_t)e->E * (e->E - 1) / 2 + 1);
-  r |= dalloc(e, &e->action_err, 1);
-  e->s.dep = nullptr;
-  e->s.sepx = nullptr;
-  e->s.sepx_cap = 0;
-  if (cfg->scenario == LSM_SCENARIO_DEPARTURES) r |= dalloc(e, &e->s.dep, n * depw(N));
-  if (r) return 1;
-  if (e->s.dep) {   // Agent.departed defaults to True (core.py:343), timers 0
-    std::vector<double> d(n * depw(N), 0.0);
-    for (size_t k = 0; k < n; ++k)
-      for (int i = 0; i < N; ++i) d[k * depw(N) + i] = 1.0;
-    HIPCHK(e, hipMemcpy(e->s.dep, d.data(), d.size() * 8, hipMemcpyHostToDevice));
-  }
-  HIPCHK(e, hipMemset(e->action_err, 0, sizeof(int32_t)));
-  {
-    // agent-agent pairs first (the only ones needing the float64 blocks), then
-    // agent-landmark, then landmark-landmark: the agent block stays in the first lane pass
-    std::vector<uint16_t> pr;
-    for (int cls = 0; cls < 3; ++cls)
-      for (int a = 0; a < e->E; ++a)
-        for (int b = a + 1; b < e->E; ++b) {
-          const int c = (a < N ? 0 : 1) + (b < N ? 0 : 1);
-          if (c == cls) pr.push_back((uint16_t)(a | (b << 8)));
-        }
-    pr.push_back(0);
-    HIPCHK(e, hipMemcpy(e->pairs, pr.data(), pr.size() * 2, hipMemcpyHostToDevice));
-  }
-  {
-    // reference initial values: prev summary (environment.py:873-881), stats and info
-    // accumulators (init_episode_agent_info), decon -1, min distances inf
-    const size_t stride = (size_t)e->s.rec_stride16 * 16;
-    std::vector<unsigned char> rec(stride, 0);
-    double* stats = (double*)(rec.data() + lp.off[1]);
-    double* winfo = (double*)(rec.data() + lp.off[2]);
-    double* gmt = (double*)(rec.data() + lp.off[4]);
-    double* minrel = (double*)(rec.data() + lp.off[5]);
-    int32_t* decon = (int32_t*)(rec.data() + lp.off[10]);
-    for (int i = 0; i < N; ++i) {
-      stats[4 * N + i] = INFINITY;
-      for (int q = 0; q < 3; ++q) winfo[q * N + i] = -1.0;
-      winfo[3 * N + i] = 0.0;
-      gmt[i] = INFINITY;
-      minrel[i] = INFINITY;
-      decon[i] = -1;
-    }
-    std::vector<unsigned char> all(n * stride);
-    for (size_t k = 0; k < n; ++k) memcpy(all.data() + k * stride, rec.data(), stride);
-    HIPCHK(e, hipMemcpy(e->s.rec, all.data(), all.size(), hipMemcpyHostToDevice));
-    std::vector<double> prev(n * 8, 0.0);
-    for (size_t k = 0; k < n; ++k) prev[k * 8 + 0] = cfg->episode_length;
-    HIPCHK(e, hipMemcpy(e->s.prev, prev.data(), prev.size() * 8, hipMemcpyHostToDevice));
-  }
-  hipLaunchKernelGGL(seed_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, e->s.mt, (int)n, cfg->seed,
-                     cfg->env_offset);
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipDeviceSynchronize());
-  e->tables_ok = !uses_hj(e) && cfg->dynamics == LSM_DOUBLE_INTEGRATOR;
-  return 0;
-}
-
-void lsm_destroy(lsm_env* e) {
-  if (!e) return;
-  for (void* p : e->allocs) (void)hipFree(p);
-  delete e;
-}
-
-// Free one of the handle's allocations (a replaced table).
-static void dfree(lsm_env* e, const void* p) {
-  if (!p) return;
-  for (size_t k = 0; k < e->allocs.size(); ++k)
-    if (e->allocs[k] == p) {
-      (void)hipFree(e->allocs[k]);
-      e->allocs.erase(e->allocs.begin() + k);
-      return;
-    }
-}
-
-static int upload_table(lsm_env* e, TableDev& T, int32_t ndim, const double* lo, const double* hi,
-                        const int32_t* shape, const int32_t* periodic, const float* values,
-                        const float* grads) {
-  if (ndim < 1 || ndim > 5) return fail(e, "table ndim must be in [1, 5]");
-  HIPCHK(e, hipDeviceSynchronize());   // a replaced table may still be read by queued launches
-  dfree(e, T.cells);
-  dfree(e, T.gcells);
-  dfree(e, T.bnd);
-  memset(&T, 0, sizeof(T));
-  T.ndim = ndim;
-  size_t nodes = 1, cells = 1;
-  for (int d = 0; d < ndim; ++d) {
-    if (shape[d] < 2) return fail(e, "table dims must have >= 2 nodes");
-    nodes *= (size_t)shape[d];
-    cells *= (size_t)(periodic[d] ? shape[d] : shape[d] - 1);
-  }
-  size_t cst = 1;
-  for (int d = ndim - 1; d >= 0; --d) {
-    T.n[d] = shape[d];
-    T.cstride[d] = (int)cst;
-    cst *= (size_t)(periodic[d] ? shape[d] : shape[d] - 1);
-    T.periodic[d] = periodic[d] ? 1 : 0;
-    const double sp = T.periodic[d] ? (hi[d] - lo[d]) / shape[d] : (hi[d] - lo[d]) / (shape[d] - 1.0);
-    T.lo[d] = (float)lo[d];
-    T.sp[d] = (float)sp;
-  }
-  // grid_pos's reciprocal path, per dimension, where it equals the division for every y = s - lo
-  // a lookup can meet: grid positions within [-4, n + 3] (non-periodic: outside, the lookup is out
-  // of the grid either way -- a faithful quotient cannot cross those bounds) or within 1e9 in
-  // magnitude (periodic: the wrap reads the position itself; beyond 1e9 grid_cell refuses it)
-  {
-    int* bad = nullptr;
-    HIPCHK(e, hipMalloc((void**)&bad, sizeof(int)));
-#ifdef LSM_DIAGNOSTIC_BUILD
-    const bool no_mdiv = getenv("LSM_NO_MDIV") != nullptr;   // A/B of the division path (variant builds)
-#else
-    const bool no_mdiv = false;   // the product reads no environment knobs
-#endif
-    for (int d = 0; d < ndim; ++d) {
-      T.rsp[d] = 1.0f / T.sp[d];
-      T.mdiv[d] = 0;
-      if (!(T.sp[d] > 0.0f) || no_mdiv) continue;
-      const float plo = T.periodic[d] ? -1.0e9f : -4.0f;
-      const float phi = T.periodic[d] ? 1.0e9f : (float)(T.n[d] + 3);
-      const float ypos = phi * T.sp[d] * 1.0001f, yneg = -plo * T.sp[d] * 1.0001f;
-      uint32_t pb, nb;
-      memcpy(&pb, &ypos, 4);
-      memcpy(&nb, &yneg, 4);
-      HIPCHK(e, hipMemset(bad, 0, sizeof(int)));
-      hipLaunchKernelGGL(mdiv_check_kernel, dim3(4096), dim3(256), 0, 0, T.sp[d], T.rsp[d], pb, nb, bad);
-      HIPCHK(e, hipGetLastError());
-      int h = 1;
-      HIPCHK(e, hipMemcpy(&h, bad, sizeof(int), hipMemcpyDeviceToHost));
-      T.mdiv[d] = h == 0 ? 1 : 0;
-    }
-    HIPCHK(e, hipFree(bad));
-  }
-  const size_t ncorner = (size_t)1 << ndim;
-  if (cells * ncorner * 2 > (size_t)INT32_MAX) return fail(e, "table too large for 32-bit cell offsets");
-  T.gw = ndim <= 4 ? 1 : 2;
-  float* dv = nullptr;
-  float4* dg = nullptr;
-  HIPCHK(e, hipMalloc((void**)&dv, nodes * 4));
-  HIPCHK(e, hipMemcpy(dv, values, nodes * 4, hipMemcpyHostToDevice));
-  if (grads) {
-    HIPCHK(e, hipMalloc((void**)&dg, nodes * T.gw * 16));
-    HIPCHK(e, hipMemcpy(dg, grads, nodes * T.gw * 16, hipMemcpyHostToDevice));
-  }
-  float* cv = nullptr;
-  float4* cg = nullptr;
-  if (dalloc(e, &cv, cells * ncorner)) return 1;
-  if (grads && dalloc(e, &cg, cells * ncorner * T.gw)) return 1;
-  const int64_t work = (int64_t)(cells * ncorner);
-  hipLaunchKernelGGL(expand_cells_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, 0, dv, dg, cv, cg,
-                     T, (int64_t)cells);
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipDeviceSynchronize());
-  HIPCHK(e, hipFree(dv));
-  if (dg) HIPCHK(e, hipFree(dg));
-  T.cells = cv;
-  T.gcells = cg;
-  return 0;
-}
-
-// Value bounds per 4^ndim-cell block (TableDev::bnd), built from the node table.
-static int upload_bounds(lsm_env* e, TableDev& T, const float* values) {
-  // 4 cells per dim: 180 KB for the full DI table (L2-resident); sel.bounds_shift for tests
-  T.bshift = e->sel.bounds_shift ? e->sel.bounds_shift : 2;
-  const int B = 1 << T.bshift;
-  int nblocks = 1;
-  for (int d = T.ndim - 1; d >= 0; --d) {
-    const int ncell = T.periodic[d] ? T.n[d] : T.n[d] - 1;
-    T.bstride[d] = nblocks;
-    nblocks *= (ncell + B - 1) / B;
-  }
-  size_t nodes = 1;
-  for (int d = 0; d < T.ndim; ++d) nodes *= (size_t)T.n[d];
-  float* dv = nullptr;
-  HIPCHK(e, hipMalloc((void**)&dv, nodes * 4));
-  HIPCHK(e, hipMemcpy(dv, values, nodes * 4, hipMemcpyHostToDevice));
-  float2* bd = nullptr;
-  if (dalloc(e, &bd, (size_t)nblocks)) return 1;
-  hipLaunchKernelGGL(bounds_kernel, dim3((nblocks + 255) / 256), dim3(256), 0, 0, dv, bd, T, nblocks);
-  HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipDeviceSynchronize());
-  HIPCHK(e, hipFree(dv));
-  T.bnd = bd;
-  return 0;
-}
-
-int lsm_set_value_table(lsm_env* e, int32_t ndim, const double* lo, const double* hi, const int32_t* shape,
-                        const int32_t* periodic, const float* values, const float* grads,
-                        double separation_distance) {
-  const int want = e->cfg.dynamics == LSM_DOUBLE_INTEGRATOR ? 4 : 5;
-  if (ndim != want) return fail(e, "value table must be 4-D (double integrator) or 5-D (airtaxi)");
-  if (!grads) return fail(e, "value table needs its gradient table");
-  if (upload_table(e, e->val, ndim, lo, hi, shape, periodic, values, grads)) return 1;
-  if (upload_bounds(e, e->val, values)) return 1;
-  e->val_sep0 = e->sep_last = separation_distance;
-  e->sep_changes = 0;
-  {
-    const LdsPlan lp = lds_plan(e->N, e->NL, e->E, e->F, e->block);
-    const int n = e->cfg.num_envs;
-    hipLaunchKernelGGL(sep_clear_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, e->s.rec, e->s.rec_stride16, n,
-                       (uint32_t)(lp.off[12] + 8 * NCUR));
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipDeviceSynchronize());
-  }
-  e->tables_ok = (e->cfg.dynamics == LSM_DOUBLE_INTEGRATOR) || e->ttr.cells != nullptr;
-  e->params_dirty = true;
-  return 0;
-}
-
-int lsm_set_ttr_table(lsm_env* e, int32_t ndim, const double* lo, const double* hi, const int32_t* shape,
-                      const int32_t* periodic, const float* values, double ttr_max) {
-  if (ndim != 4) return fail(e, "TTR table must be 4-D");
-  if (upload_table(e, e->ttr, ndim, lo, hi, shape, periodic, values, nullptr)) return 1;
-  e->ttr_max = ttr_max;
-  e->tables_ok = !uses_hj(e) || e->val.cells != nullptr;
-  e->params_dirty = true;
-  return 0;
-}
-
-int lsm_bind_output(lsm_env* e, int32_t slot, void* ptr, size_t bytes) {
-  if (slot < 0 || slot >= LSM_NUM_OUT) return fail(e, "bad output slot");
-  const size_t need = lsm_output_bytes(e, slot);
-  if (ptr && bytes < need) return fail(e, "output buffer too small for slot " + std::to_string(slot));
-  e->out_ptr[slot] = ptr;
-  e->params_dirty = true;
-  e->out_bytes[slot] = bytes;
-  return 0;
-}
-
-int lsm_bind_output_ring(lsm_env* e, int32_t slot, void* base, size_t stride_bytes, int32_t count,
-                         int32_t index_offset) {
-  if (!e) return 1;
-  if (slot < 0 || slot >= LSM_NUM_OUT) return fail(e, "bad output slot");
-  if (slot == LSM_OUT_RESET_FLAG || slot == LSM_OUT_EP_INFO || slot == LSM_OUT_EDGES ||
-      slot == LSM_OUT_DEBUG_STAMPS || slot == LSM_OUT_DEPARTED || slot == LSM_OUT_ADJ_NNZ)
-    return fail(e, "slot " + std::to_string(slot) + " cannot be ring-bound");
-  if (count <= 0 || !base) {   // unbind
-    e->ring_count[slot] = 0;
-  } else {
-    if (stride_bytes < lsm_output_bytes(e, slot))
-      return fail(e, "ring stride smaller than slot " + std::to_string(slot) + "'s output");
-    e->ring_base[slot] = base;
-    e->ring_stride[slot] = stride_bytes;
-    e->ring_count[slot] = count;
-    e->ring_off[slot] = index_offset;
-  }
-  int len = 0;
-  for (int s = 0; s < LSM_NUM_OUT; ++s)
-    if (e->ring_count[s] > 0) len = std::max(len, e->ring_count[s] - e->ring_off[s]);
-  e->ring_len = len;
-  if (e->ring_sel >= len) e->ring_sel = -1;
-  e->params_dirty = true;
-  return 0;
-}
-
-int lsm_select_ring(lsm_env* e, int32_t index) {
-  if (!e) return 1;
-  if (index < -1 || index >= e->ring_len)
-    return fail(e, "ring index " + std::to_string(index) + " outside [-1, " + std::to_string(e->ring_len) + ")");
-  e->ring_sel = index;
-  return 0;
-}
-
-static int check_ready(lsm_env* e, bool stepping) {
-  if (!e->tables_ok) return fail(e, "HJ value table (filter on) / TTR table (airtaxi) not set");
-  const int req[] = {LSM_OUT_OBS, LSM_OUT_NODE_OBS, LSM_OUT_ADJ, LSM_OUT_REWARD, LSM_OUT_DONE,
-                     LSM_OUT_RESET_FLAG, LSM_OUT_EP_INFO, LSM_OUT_INFO};
-  for (int s : req)
-    if (!e->out_ptr[s]) return fail(e, "output slot " + std::to_string(s) + " not bound");
-  if (e->cfg.adj_layout == LSM_ADJ_COMPACT && !e->out_ptr[LSM_OUT_ADJ_MASK])
-    return fail(e, "compact adjacency layout needs LSM_OUT_ADJ_MASK bound");
-  if (e->cfg.collision_forces && !e->out_ptr[LSM_OUT_COLLISION_FORCE])
-    return fail(e, "collision_forces needs LSM_OUT_COLLISION_FORCE bound");
-  if (e->block && e->out_ptr[LSM_OUT_ADJ_NNZ])
-    return fail(e, "LSM_OUT_ADJ_NNZ is written by the one-wave and team kernels (E <= 64); the workgroup-per-env "
-                   "kernel's edge lists take lsm_edges_count's pass");
-  (void)stepping;
-  return 0;
-}
-
-// An env's shift chain grows only at its resets, by one entry per change of the separation it
-// resets with, so the changes across the calls' curriculum blocks since the table upload bound every
-// chain. The record holds KSEP shifts; before a launch that could write shift k >= KSEP the per-env
-// overflow rows (StateDev::sepx) are grown, stream-ordered, keeping the shifts already there. The
-// reference has no bound (HjDataHandle.update_separation_distance shifts the table in place,
-// safety_filter.py:170-174); neither has this.
-static int sep_check(lsm_env* e, const lsm_curriculum* cur, hipStream_t st) {
-  if (!uses_hj(e)) return 0;
-  if (cur->separation_distance == e->sep_last) return 0;
-  // the overflow rows are grown first; the change is recorded only once they can hold it, so a
-  // failed allocation leaves the handle as it was (a retry grows them again)
-  const int changes = e->sep_changes + 1;
-  const uint32_t need = changes > KSEP ? (uint32_t)(changes - KSEP) : 0;
-  if (need > e->s.sepx_cap) {
-    const uint32_t cap = std::max<uint32_t>(std::max<uint32_t>(2 * e->s.sepx_cap, 16), need);
-    const size_t n = (size_t)e->cfg.num_envs;
-    double* nx = nullptr;
-    if (dalloc(e, &nx, n * cap)) return 1;
-    if (e->s.sepx) {
-      if (hipMemcpy2DAsync(nx, (size_t)cap * 8, e->s.sepx, (size_t)e->s.sepx_cap * 8, (size_t)e->s.sepx_cap * 8, n,
-                           hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipStreamSynchronize(st) != hipSuccess) {
-        dfree(e, nx);
-        return fail(e, "growing the HJ separation shift rows failed");
-      }
-      dfree(e, e->s.sepx);
-    }
-    e->s.sepx = nx;
-    e->s.sepx_cap = cap;
-    e->params_dirty = true;
-  }
-  e->sep_changes = changes;
-  e->sep_last = cur->separation_distance;
-  return 0;
-}
-
-// output pointers of ring index i (see lsm_env::ring_*)
-static void apply_ring(const lsm_env* e, int i, KParams& P) {
-  auto at = [&](int slot, void* plain) -> void* {
-    if (e->ring_count[slot] <= 0) return plain;
-    const int j = i + e->ring_off[slot];
-    if (j < 0 || j >= e->ring_count[slot]) return plain;
-    return (char*)e->ring_base[slot] + (size_t)j * e->ring_stride[slot];
-  };
-  P.o.obs = (float*)at(LSM_OUT_OBS, P.o.obs);
-  P.o.node = (float*)at(LSM_OUT_NODE_OBS, P.o.node);
-  P.o.adj = (float*)at(LSM_OUT_ADJ, P.o.adj);
-  P.o.rew = (float*)at(LSM_OUT_REWARD, P.o.rew);
-  P.o.dones = (uint8_t*)at(LSM_OUT_DONE, P.o.dones);
-  P.o.info = (double*)at(LSM_OUT_INFO, P.o.info);
-  P.o.state = (double*)at(LSM_OUT_STATE, P.o.state);
-  P.o.adjmask = (uint64_t*)at(LSM_OUT_ADJ_MASK, P.o.adjmask);
-  P.o.share_obs = (float*)at(LSM_OUT_SHARE_OBS, P.o.share_obs);
-  P.o.masks = (float*)at(LSM_OUT_MASKS, P.o.masks);
-  P.o.active_masks = (float*)at(LSM_OUT_ACTIVE_MASKS, P.o.active_masks);
-  P.o.cforce = (double*)at(LSM_OUT_COLLISION_FORCE, P.o.cforce);
-}
-
-static int launch(lsm_env* e, KStep& L, hipStream_t st) {
-  size_t env_lds = lds_plan(e->N, e->NL, e->E, e->F, e->block, e->lean).bytes;
-  if (e->team) env_lds = team_env_bytes(env_lds, e->N);
-  if (e->cfg.scenario == LSM_SCENARIO_DEPARTURES) env_lds += dep_lds_bytes(e->N);
-  if (e->block ? env_lds > 160 * 1024
-               : (e->team ? env_lds * e->team > 160 * 1024 : env_lds * (WAVE / e->lpe) > 65536))
-    return fail(e, "LDS footprint too large");
-  if (e->params_dirty) {   // outputs / tables changed: refresh the device copy (stream-ordered)
-    KParams P;
-    fill_params(e, P);
-    P.lds_env_bytes = (uint32_t)env_lds;
-    HIPCHK(e, hipMemcpyAsync(e->dparams, &P, sizeof(P), hipMemcpyHostToDevice, st));
-    if (e->ring_len > 0) {
-      if (e->ring_cap < e->ring_len) {
-        if (dalloc(e, &e->dring, (size_t)e->ring_len)) return 1;
-        e->ring_cap = e->ring_len;
-      }
-      std::vector<KParams> ring((size_t)e->ring_len);
-      for (int i = 0; i < e->ring_len; ++i) {
-        ring[i] = P;
-        apply_ring(e, i, ring[i]);
-      }
-      HIPCHK(e, hipMemcpyAsync(e->dring, ring.data(), sizeof(KParams) * ring.size(), hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(e, hipStreamSynchronize(st));
-    e->params_dirty = false;
-  }
-  L.stop_after = -1;
-#ifdef LSM_STAMPS
-  if (const char* v = getenv("LSM_STOP_AFTER")) L.stop_after = atoi(v);
-#endif
-  const bool di = e->cfg.dynamics == LSM_DOUBLE_INTEGRATOR;
-  if (e->block) {
-    // workgroup per env; compile-time N = 64 (config 5) or the generic kernel
-    const bool spec64 = e->N == 64 && e->L == 2 && !e->generic_only;
-    int rc;
-    if (di) rc = spec64 ? launch_block_t<0, 64>(e, L, env_lds, st) : launch_block_t<0, 0>(e, L, env_lds, st);
-    else rc = spec64 ? launch_block_t<1, 64>(e, L, env_lds, st) : launch_block_t<1, 0>(e, L, env_lds, st);
-    if (rc) return rc;
-    HIPCHK(e, hipGetLastError());
-    return 0;
-  }
-  if (e->team) {
-    int rc = 1;
-    // fill_params' P.rext: the kernel without the optional-reward block unless it can run
-    const bool rext = e->cfg.reward_terms != 0 || e->cfg.collaborative;
-    if (di) {
-      if (e->team == 8) rc = rext ? launch_team_t<0, 8, 8, true>(e, L, env_lds, st) : launch_team_t<0, 8, 8, false>(e, L, env_lds, st);
-      else if (e->team == 4) rc = rext ? launch_team_t<0, 8, 4, true>(e, L, env_lds, st) : launch_team_t<0, 8, 4, false>(e, L, env_lds, st);
-      else rc = rext ? launch_team_t<0, 8, 2, true>(e, L, env_lds, st) : launch_team_t<0, 8, 2, false>(e, L, env_lds, st);
-    } else {
-      if (e->team == 4) rc = rext ? launch_team_t<1, 16, 4, true>(e, L, env_lds, st) : launch_team_t<1, 16, 4, false>(e, L, env_lds, st);
-      else rc = rext ? launch_team_t<1, 16, 2, true>(e, L, env_lds, st) : launch_team_t<1, 16, 2, false>(e, L, env_lds, st);
-    }
-    if (rc) return rc;
-    HIPCHK(e, hipGetLastError());
-    return 0;
-  }
-  // specialised kernels (compile-time N, L = 2, one env per wave) for the BASELINE agent
-  // counts; everything else runs the generic kernel (runtime dims, LPE 64/32/16)
-  const bool spec = e->lpe == 64 && e->L == 2 && !e->generic_only;
-  const bool spec32 = e->lpe == 32 && e->L == 2 && !e->generic_only;
-  if (spec32 && di && e->N == 8) launch_t<0, 32, 8>(e, L, env_lds, st);
-  else if (spec32 && !di && e->N == 16) launch_t<1, 32, 16>(e, L, env_lds, st);
-  else if (spec && di && e->N == 3) launch_t<0, 64, 3>(e, L, env_lds, st);
-  else if (spec && di && e->N == 8) launch_t<0, 64, 8>(e, L, env_lds, st);
-  else if (spec && !di && e->N == 3) launch_t<1, 64, 3>(e, L, env_lds, st);
-  else if (spec && !di && e->N == 16) launch_t<1, 64, 16>(e, L, env_lds, st);
-  else {
-    const int k = (di ? 0 : 4) + (e->lpe == 64 ? 0 : e->lpe == 32 ? 1 : e->lpe == 16 ? 2 : 3);
-    switch (k) {
-      case 0: launch_t<0, 64, 0>(e, L, env_lds, st); break;
-      case 1: launch_t<0, 32, 0>(e, L, env_lds, st); break;
-      case 2: launch_t<0, 16, 0>(e, L, env_lds, st); break;
-      case 4: launch_t<1, 64, 0>(e, L, env_lds, st); break;
-      case 5: launch_t<1, 32, 0>(e, L, env_lds, st); break;
-      case 6: launch_t<1, 16, 0>(e, L, env_lds, st); break;
-      default: return fail(e, "unsupported lanes-per-env");
-    }
-  }
-  HIPCHK(e, hipGetLastError());
-  return 0;
-}
-
-#ifndef LSM_BUILD_ID
-#define LSM_BUILD_ID "unknown"
-#endif
-const char* lsm_build_id(void) { return LSM_BUILD_ID; }
-
-int lsm_test_set_mt_stage(lsm_env* e, int32_t words) {
-  if (!e) return 1;
-  e->mt_stage = std::max(1, std::min(2 * MT_N, (int)words));
-  e->params_dirty = true;
-  return 0;
-}
-
-int lsm_test_read_value_bounds(lsm_env* e, float* lo_hi, int32_t cap_blocks, int32_t nblocks_per_dim[5],
-                               int32_t* bshift) {
-  if (!e) return 1;
-  const TableDev& T = e->val;
-  if (!T.bnd || T.ndim < 1) return fail(e, "read value bounds: no value table set");
-  if (!lo_hi || !nblocks_per_dim || !bshift) return fail(e, "read value bounds: null argument");
-  const int B = 1 << T.bshift;
-  int64_t nblocks = 1;
-  for (int d = 0; d < 5; ++d) {
-    nblocks_per_dim[d] = 0;
-    if (d >= T.ndim) continue;
-    const int ncell = T.periodic[d] ? T.n[d] : T.n[d] - 1;
-    nblocks_per_dim[d] = (ncell + B - 1) / B;
-    nblocks *= nblocks_per_dim[d];
-  }
-  *bshift = T.bshift;
-  if ((int64_t)cap_blocks < nblocks) return fail(e, "read value bounds: capacity below the table's block count");
-  HIPCHK(e, hipDeviceSynchronize());
-  HIPCHK(e, hipMemcpy(lo_hi, T.bnd, (size_t)nblocks * sizeof(float2), hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The kernel launch() dispatches to for this handle (same selection as launch()).
-const char* lsm_kernel_name(const lsm_env* e) {
-  static thread_local std::string name;
-  if (!e) return "";
-  const bool di = e->cfg.dynamics == LSM_DOUBLE_INTEGRATOR;
-  const int D = di ? 0 : 1;
-  const char* rext = (e->cfg.reward_terms != 0 || e->cfg.collaborative) ? "true" : "false";
-  if (e->block) {
-    const bool spec64 = e->N == 64 && e->L == 2 && !e->generic_only;
-    const bool nis1 = e->cfg.num_internal_step <= 1;
-    name = "rollout_block_kernel<" + std::to_string(D) + ", " + std::to_string(spec64 ? 64 : 0) + ", " +
-           (nis1 ? "true" : "false") + ", " + (nis1 ? rext : "true") + ">";
-  } else if (e->team) {
-    name = "rollout_team_kernel<" + std::to_string(D) + ", " + std::to_string(e->N) + ", " + std::to_string(e->team) +
-           ", " + rext + ">";
-  } else {
-    const bool specN = e->L == 2 && !e->generic_only &&
-                       ((e->lpe == 64 && ((di && (e->N == 3 || e->N == 8)) || (!di && (e->N == 3 || e->N == 16)))) ||
-                        (e->lpe == 32 && ((di && e->N == 8) || (!di && e->N == 16))));
-    name = "rollout_kernel<" + std::to_string(D) + ", " + std::to_string(e->lpe) + ", " +
-           std::to_string(specN ? e->N : 0) + ">";
-  }
-  return name.c_str();
-}
-
-int lsm_set_agent_state(lsm_env* e, int32_t env_index, const double* state, const int32_t* reached,
-                        void* stream) {
-  if (!e || !state) return 1;
-  if (env_index < 0 || env_index >= e->cfg.num_envs) return fail(e, "env_index out of range");
-  HIPCHK(e, hipStreamSynchronize((hipStream_t)stream));
-  const LdsPlan lp = lds_plan(e->N, e->NL, e->E, e->F, e->block);
-  std::vector<unsigned char> rec(lp.rec);
-  float4* dev = e->s.rec + (size_t)env_index * e->s.rec_stride16;
-  HIPCHK(e, hipMemcpy(rec.data(), dev, lp.rec, hipMemcpyDeviceToHost));
-  double* ps = (double*)(rec.data() + lp.off[0]);   // record field 0: agent state [4][N]
-  for (int i = 0; i < e->N; ++i)
-    for (int c = 0; c < 4; ++c) ps[c * e->N + i] = state[i * 4 + c];
-  if (reached) {
-    int32_t* rp = (int32_t*)(rec.data() + lp.off[8]);   // record field 8: reached_goal
-    for (int i = 0; i < e->N; ++i) rp[i] = reached[i];
-  }
-  ((int32_t*)(rec.data() + lp.off[11]))[1] = 1;   // step slot: distances recomputed, unmasked
-  HIPCHK(e, hipMemcpy(dev, rec.data(), lp.rec, hipMemcpyHostToDevice));
-  return 0;
-}
-
-int lsm_reset(lsm_env* e, const lsm_curriculum* cur, void* stream) {
-  if (!e || !cur) return 1;
-  if (e->cfg.scenario != LSM_SCENARIO_TRAIN) return fail(e, "layout scenario: reset with lsm_reset_layout");
-  if (check_ready(e, false)) return 1;
-  if (sep_check(e, cur, (hipStream_t)stream)) return 1;
-  KStep L;
-  memset(&L, 0, sizeof(L));
-  memcpy(L.cur_new, cur, sizeof(double) * NCUR);
-  L.mode = 1;
-  L.emit_edges = 0;
-  return launch(e, L, (hipStream_t)stream);
-}
-
-int lsm_reset_layout(lsm_env* e, const lsm_curriculum* cur, const double* layout, void* stream) {
-  if (!e || !cur) return 1;
-  if (e->cfg.scenario == LSM_SCENARIO_TRAIN) return fail(e, "lsm_reset_layout needs a layout scenario");
-  if (!layout) return fail(e, "null layout");
-  if (check_ready(e, false)) return 1;
-  if (sep_check(e, cur, (hipStream_t)stream)) return 1;
-  KStep L;
-  memset(&L, 0, sizeof(L));
-  memcpy(L.cur_new, cur, sizeof(double) * NCUR);
-  L.mode = 2;
-  L.layout = layout;
-  return launch(e, L, (hipStream_t)stream);
-}
-
-int lsm_step(lsm_env* e, const void* actions, int32_t kind, const lsm_curriculum* cur, void* stream) {
-  if (!e || !actions || !cur) return fail(e, "null argument");
-  if (kind < 0 || kind > 2) return fail(e, "bad action kind");
-  if (check_ready(e, true)) return 1;
-  // a step's curriculum block is used only by its auto-resets: without them no chain can grow
-  if (e->cfg.auto_reset && sep_check(e, cur, (hipStream_t)stream)) return 1;
-  KStep L;
-  memset(&L, 0, sizeof(L));
-  memcpy(L.cur_new, cur, sizeof(double) * NCUR);
-  L.mode = 0;
-  L.action_kind = kind;
-  L.actions = actions;
-  L.emit_edges = e->cfg.emit_edges && e->out_ptr[LSM_OUT_EDGES] != nullptr;
-  return launch(e, L, (hipStream_t)stream);
-}
-
-int32_t lsm_action_errors(lsm_env* e, void* stream) {
-  if (!e) return -1;
-  int32_t v = 0;
-  if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return -1;
-  if (hipMemcpy(&v, e->action_err, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  if (v && hipMemset(e->action_err, 0, sizeof(int32_t)) != hipSuccess) return -1;
-  return v;
-}
-
-int lsm_host_rk45_di(const double* y0, double a0, double a1, double dt, double* y_out) {
-  double y[4] = {y0[0], y0[1], y0[2], y0[3]};
-  const int n = rk45_di(y, a0, a1, dt);
-  for (int i = 0; i < 4; ++i) y_out[i] = y[i];
-  return n;
-}
-
-double lsm_host_glibc_pow(double x, double y) { return glibc_pow(x, y); }
-
-int lsm_host_philox4x32(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
-  philox4x32_10(ctr, key, out);
-  return 0;
-}
-
-int lsm_host_philox_uniforms(uint32_t key, uint32_t reset_index, int32_t count, double lo, double hi,
-                             double* out) {
-  Philox m;
-  m.init(key, reset_index);
-  for (int k = 0; k < count; ++k) out[k] = m.uniform(lo, hi);
-  return 0;
-}
-
-int lsm_host_mt_uniforms(uint32_t seed, int32_t count, double lo, double hi, double* out) {
-  HostMT m;
-  m.seed(seed);
-  for (int k = 0; k < count; ++k) out[k] = m.uniform(lo, hi);
-  return 0;
-}
-
-int lsm_host_scenario(const lsm_config* cfg, const lsm_curriculum* cur, uint32_t seed, double* agent_state,
-                      double* landmarks) {
-  const int N = cfg->num_agents, L = cfg->num_landmarks, NL = N * L;
-  if (N < 2 || N > BMAXN || L < 2 || L > MAX_L) return 1;
-  ScenarioParams sp;
-  const bool di = cfg->dynamics == LSM_DOUBLE_INTEGRATOR;
-  sp.dyn = di ? 0 : 1; sp.N = N; sp.L = L; sp.world_size = cfg->world_size;
-  sp.coordination_range = di ? 4.0 : 3 * 1.60934;
-  sp.goal_speed_min = di ? 0.1 : 60 * 0.514444 * 0.001;
-  sp.goal_speed_max = di ? 0.5 : 110 * 0.514444 * 0.001;
-  sp.ratio_airtaxi = cur->ratio_airtaxi; sp.ratio_scenario = cur->ratio_scenario;
-  sp.pi = 3.141592653589793; sp.two_pi = 2 * sp.pi;
-  sp.d2lo = sp.d2hi = 0.0;   // (the device draw's squared band; random_scenario tests d itself)
-  std::vector<double> st(4 * N), lm(4 * NL), ws(SCEN_WS);
-  if (cfg->rng == LSM_RNG_PHILOX) {   // the device's first reset (reset index 0) of this seed
-    Philox m;
-    m.init(seed, 0);
-    random_scenario(m, sp, st.data(), lm.data(), ws.data());
-  } else {
-    HostMT m;
-    m.seed(seed);
-    random_scenario(m, sp, st.data(), lm.data(), ws.data());
-  }
-  for (int i = 0; i < N; ++i)
-    for (int c = 0; c < 4; ++c) agent_state[i * 4 + c] = st[c * N + i];
-  for (int k = 0; k < NL; ++k)
-    for (int c = 0; c < 4; ++c) landmarks[k * 4 + c] = lm[c * NL + k];
-  return 0;
-}
-
-}  // extern "C"
-
-#endif  // LSM_HOST_PART
+#define LSM_CAT_(a, b) a##b
+#define LSM_CAT(a, b) LSM_CAT_(a, b)
+#define LSM_INST_W(d, lpe, nt) template int launch_t<d, lpe, nt>(LSM_LAUNCH_ARGS);
+#define LSM_INST_T(d, nt, g, rext) template int launch_team_t<d, nt, g, rext>(LSM_LAUNCH_ARGS);
+#define LSM_INST_B(d, nt, nis1, rext) template int launch_block_t<d, nt, nis1, rext>(LSM_LAUNCH_ARGS);
+LSM_CAT(LSM_KERNELS_, LSM_PART)(LSM_INST_W, LSM_INST_T, LSM_INST_B)

@@ -19,20 +19,10 @@
 //                          info, episode stats;   other waves: speculative adjacency stores
 //   W  E (each env's wave) info rows out, dones / masks, then the auto-reset or the graph outputs
 //
-// LDS: the workgroup holds G env blocks of `lds_env_bytes`, padded (team_env_bytes) so that the
+// LDS: the workgroup holds G env blocks of `lds_env_bytes`, padded (team_env_bytes, lsm_params.h) so that the
 // agent wave's lanes of different envs fall on different banks.
 #pragma once
 // (included inside namespace lsm)
-
-// Env block stride for the team kernel: a multiple of 8 NT bytes with an odd quotient, so the
-// 8-B per-agent fields of envs g = 0, 1, ... of one 32-lane ds_read_b64 group (256-B bank row)
-// start on distinct bank offsets.
-__host__ __device__ inline size_t team_env_bytes(size_t bytes, int N) {
-  const size_t u = 8 * (size_t)N;
-  size_t q = (bytes + u - 1) / u;
-  if ((q & 1) == 0) ++q;
-  return q * u;
-}
 
 // Team kernels target 4 waves / SIMD for the double integrator (<= 128 VGPRs, as rollout_kernel)
 // and 2 for airtaxi.

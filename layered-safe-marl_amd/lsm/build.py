@@ -2,9 +2,9 @@
 
 ``python -m lsm.build`` (from ``layered-safe-marl_amd/``) or ``__graft_entry__.build()``.
 
-The rollout translation unit instantiates ~25 kernels; it is compiled as ``ROLLOUT_PARTS``
-objects in parallel (``-DLSM_PART=0`` the host code, ``-DLSM_PART=g`` kernel group g, see the
-group table in ``csrc/lsm_rollout.hip``) and linked with the other units.
+The rollout is ``ROLLOUT_PARTS`` objects compiled in parallel: part 0 is the host side of the C ABI
+(``csrc/lsm_host.hip``), part g > 0 is ``csrc/lsm_rollout.hip`` with ``-DLSM_PART=g``, the step kernels
+of build group g (the kernel table in ``csrc/lsm_kernels.h``). They are linked with the other units.
 """
 from __future__ import annotations
 
@@ -14,10 +14,12 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "csrc")
-SRC = os.path.join(CSRC, "lsm_rollout.hip")   # the rollout TU
+SRC = os.path.join(CSRC, "lsm_rollout.hip")   # the step kernels (parts 1..8)
+HOST_SRC = os.path.join(CSRC, "lsm_host.hip")   # the host side of the C ABI (part 0)
 OUT = os.path.join(CSRC, "liblsm_rollout.so")
 HDR = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "lsm_rollout.h")
-ROLLOUT_DEPS = ["lsm_numeric.h", "lsm_scenario.h", "lsm_block.h", "lsm_rk45.h", "lsm_pow_tables.h", "lsm_team.h"]
+ROLLOUT_DEPS = ["lsm_params.h", "lsm_kernels.h", "lsm_numeric.h", "lsm_scenario.h", "lsm_block.h", "lsm_rk45.h",
+                "lsm_pow_tables.h", "lsm_team.h"]
 ROLLOUT_PARTS = 9
 # the other translation units -> their dependencies (each compiled to its own object, then linked)
 UNITS = {
@@ -31,7 +33,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          # reproduce numpy's float64 expression order exactly; explicit fma() only where
          # OpenBLAS fuses (lsm_numeric.h)
          "-ffp-contract=off", "-Wno-unused-result", "-Wno-unused-function"]
-# Variant / diagnostic builds define this; csrc/lsm_rollout.hip refuses its diagnostic switches
+# Variant / diagnostic builds define this; csrc/lsm_params.h refuses the diagnostic switches
 # (LSM_XP_*: bounds with wrong results, LSM_STAMPS) without it, so the product build cannot get one.
 DIAG_DEFINE = "LSM_DIAGNOSTIC_BUILD"
 
@@ -52,7 +54,7 @@ def _part_obj(part: int, tag: str = "") -> str:
 
 
 def _rollout_deps():
-    return [SRC, HDR] + [os.path.join(CSRC, d) for d in ROLLOUT_DEPS]
+    return [SRC, HOST_SRC, HDR] + [os.path.join(CSRC, d) for d in ROLLOUT_DEPS]
 
 
 def _run_parallel(jobs, verbose=True):
@@ -77,8 +79,8 @@ def _run_parallel(jobs, verbose=True):
 
 
 def build_id(defines=()) -> str:
-    """sha256 of the step kernel's sources, the header, the compiler flags and the variant's -D
-    flags (16 hex digits): lsm_build_id() of the library built from them."""
+    """sha256 of the step kernels' and the host ABI's sources, the header, the compiler flags and the
+    variant's -D flags (16 hex digits): lsm_build_id() of the library built from them."""
     import hashlib
     h = hashlib.sha256()
     for f in _rollout_deps():
@@ -95,8 +97,9 @@ def _rollout_jobs(defines=(), tag="", force=True, parts=None):
     for part in (range(ROLLOUT_PARTS) if parts is None else parts):
         o = _part_obj(part, tag)
         if force or _stale(o, _rollout_deps()):
+            src = ["-DLSM_PART=%d" % part, "lsm_rollout.hip"] if part else ["lsm_host.hip"]
             cmd = [HIPCC] + FLAGS + ["-D%s" % d for d in defines] + ['-DLSM_BUILD_ID="%s"' % bid] + \
-                ["-DLSM_PART=%d" % part, "-c", "-o", o + ".tmp", "lsm_rollout.hip"]
+                ["-c", "-o", o + ".tmp"] + src
             jobs.append((cmd, o))
     return jobs
 

@@ -38,7 +38,7 @@ EXPORTED = ("lsm_create", "lsm_destroy", "lsm_last_error", "lsm_set_value_table"
             "lsm_buffer_last_error", "lsm_host_rk45_di", "lsm_host_glibc_pow", "lsm_action_errors",
             "lsm_kernel_name", "lsm_reset_layout", "lsm_layout_doubles", "lsm_host_philox_uniforms",
             "lsm_host_philox4x32", "lsm_episode_summary", "lsm_build_id", "lsm_test_set_mt_stage",
-            "lsm_create_select", "lsm_edges_scan_emit", "lsm_test_read_value_bounds")
+            "lsm_create_select", "lsm_edges_scan_emit", "lsm_test_read_value_bounds", "lsm_kernel_name_for")
 
 
 class LsmConfig(C.Structure):
@@ -124,6 +124,7 @@ def load_library(path: str = LIB_PATH):
         "lsm_host_glibc_pow": (D, [D, D]),
         "lsm_action_errors": (I32, [P, P]),
         "lsm_kernel_name": (C.c_char_p, [P]),
+        "lsm_kernel_name_for": (I32, [C.POINTER(LsmConfig), C.POINTER(LsmKernelSelect), C.c_char_p, SZ]),
         "lsm_reset_layout": (I32, [P, C.POINTER(LsmCurriculum), P, P]),
         "lsm_layout_doubles": (I32, [P]),
         "lsm_host_philox_uniforms": (I32, [U32, U32, I32, D, D, P]),

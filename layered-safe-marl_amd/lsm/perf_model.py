@@ -3,7 +3,7 @@
 Counts the bytes that MUST cross HBM for one env-step of the reference-layout
 path, per env:
 
-* the env's persistent record (lsm_rollout.hip StateDev / lds_plan), read whole and
+* the env's persistent record (lsm_params.h StateDev / lds_plan), read whole and
   written back up to the curriculum block: agent state 4N f64, episode stats 6N f64,
   info accumulators 4N f64, travel distance / goal_min_time / min relative distance /
   action diff N f64 each, done / reached / safety flag / deconflicting index N i32

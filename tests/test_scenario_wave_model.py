@@ -224,7 +224,7 @@ def test_raw_words_are_the_uniform_stream():
 
 
 def _sq_band(dmin, dmax):
-    """fill_params' squared-distance band (lsm_rollout.hip): the largest s with sqrt(s) <= dmin and
+    """fill_params' squared-distance band (lsm_host.hip): the largest s with sqrt(s) <= dmin and
     the smallest s with sqrt(s) >= dmax, for the correctly rounded sqrt."""
     lo = dmin * dmin
     while np.sqrt(lo) > dmin:
