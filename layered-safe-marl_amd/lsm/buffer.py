@@ -11,7 +11,13 @@ env's output slots are ring-bound to the buffer (``lsm_bind_output_ring``), one 
 buffer row, so selecting a row is a host-side pointer choice. With a centralized critic
 (``use_centralized_V``, the reference default) the kernel also writes that row's share_obs, masks and
 active_masks (optional output slots); otherwise ``lsm_buffer_insert`` (HIP) derives them from the
-step's obs and dones. agent_id / share_agent_id rows are constant and filled once. Policy-side fields (rnn states, actions, values, log-probs) stay with the learner.
+step's obs and dones. agent_id / share_agent_id rows are constant and filled once. Policy-side fields (rnn states, actions, log-probs) stay with the learner.
+
+Between the last env step and the first ppo_update the buffer also does what the reference does with
+it (``include/lsm_learner.h``): ``compute_returns`` (``graph_buffer.py:285-366``, ``csrc/lsm_returns.hip``),
+``advantages`` (``graph_mappo.py:258-268``) and ``feed_forward_generator`` (``graph_buffer.py:368-453``,
+one ``lsm_buffer_gather`` launch per minibatch, ``csrc/lsm_gather.hip``), on ``value_preds`` handed to
+``insert_step``.
 """
 from __future__ import annotations
 
@@ -54,6 +60,11 @@ class DeviceGraphBuffer:
         self.masks = torch.ones((T1, n, N, 1), dtype=f32, device=dev)
         self.bad_masks = torch.ones_like(self.masks)
         self.active_masks = torch.ones_like(self.masks)
+        # learner-side rows (graph_buffer.py:125-129): the critic's values come in through insert_step,
+        # compute_returns fills returns
+        self.value_preds = torch.zeros((T1, n, N, 1), dtype=f32, device=dev)
+        self.returns = torch.zeros_like(self.value_preds)
+        self._adv_ws = None   # advantages(): the partial-sum workspace, allocated on first use
         self.step = 0
         # agent ids are the same every row (the env returns agent index j for agent j)
         ids = torch.arange(N, dtype=i32, device=dev)
@@ -112,11 +123,15 @@ class DeviceGraphBuffer:
         self.step = 0
         return ep
 
-    def insert_step(self, actions, num_current_episode=None):
+    def insert_step(self, actions, num_current_episode=None, value_preds=None):
         """env.step + GMPERunner.insert's env-side rows for buffer step t = self.step: obs,
         node_obs, adj, share_obs, agent_id, share_agent_id, masks, active_masks at t+1 and
-        rewards at t. Returns (dones [n, N] u8, (info, reset_flag, ep_info)) device tensors."""
+        rewards at t. value_preds (the critic's values for step t, n * N floats), when given, is
+        copied into value_preds[t] first. Returns (dones [n, N] u8, (info, reset_flag, ep_info))
+        device tensors."""
         t = self.step
+        if value_preds is not None:
+            self.value_preds[t].copy_(self._as_f32(value_preds).reshape(self.value_preds[t].shape))
         self._select(t + 1)
         self.env.step_async(actions, num_current_episode)
         self.env.step_wait()
@@ -133,3 +148,164 @@ class DeviceGraphBuffer:
             fields.append(self.adj_mask)
         for f in fields:
             f[0].copy_(f[-1])
+
+    # ---- learner hand-off (include/lsm_learner.h) ------------------------------------------------
+
+    def _as_f32(self, x):
+        import torch
+        return torch.as_tensor(x, dtype=torch.float32, device=self.env.device)
+
+    def _denorm(self, value_normalizer):
+        """The kernels' device float32 [2] = {sqrt(var), mean}, or None. From a normaliser object it is
+        built with torch ops and no .item(): on the env's stream with no synchronisation when its
+        tensors are on the env's device. CPU tensors, and a (scale, mean) pair of Python numbers, go
+        through a host-to-device copy, which blocks the host; a device [2] tensor is used as it is."""
+        import torch
+        vn = value_normalizer
+        if vn is None:
+            return None
+        if hasattr(vn, "running_mean_var"):
+            mean, var = vn.running_mean_var()
+            if mean.numel() != 1 or var.numel() != 1:
+                raise BufferError("value_normalizer.running_mean_var() must return 1-element tensors")
+            d = torch.stack([torch.sqrt(var.detach()).reshape(()), mean.detach().reshape(())])
+            return d.to(device=self.env.device, dtype=torch.float32).contiguous()
+        if isinstance(vn, torch.Tensor):
+            if vn.shape != (2,) or vn.dtype != torch.float32 or vn.device != self.env.device:
+                raise BufferError("a denorm tensor must be float32 [2] = (scale, mean) on the env's device")
+            return vn.contiguous()
+        scale, mean = vn
+        return torch.tensor([float(scale), float(mean)], dtype=torch.float32, device=self.env.device)
+
+    @staticmethod
+    def _ptr(t):
+        return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def compute_returns(self, next_value, value_normalizer=None, *, gamma, gae_lambda, use_gae=True,
+                        use_proper_time_limits=False):
+        """GraphReplayBuffer.compute_returns (graph_buffer.py:285-366) on the device, bit for bit: fills
+        returns[0..T-1] (and value_preds[T] with use_gae, returns[T] without) from rewards, value_preds,
+        masks and bad_masks. value_normalizer: None, an object with running_mean_var() (ValueNorm,
+        PopArt), a (scale, mean) pair or a device float32 [2] tensor. Stream-ordered. The call itself never
+        synchronises; a normaliser or next_value that lives on the host costs a blocking upload (_denorm)."""
+        env = self.env
+        nv = self._as_f32(next_value).reshape(env.num_envs * env.N).contiguous()
+        den = self._denorm(value_normalizer)
+        cfg = capi.LsmReturnsConfig(gamma=float(gamma), gae_lambda=float(gae_lambda), use_gae=int(bool(use_gae)),
+                                    use_proper_time_limits=int(bool(use_proper_time_limits)))
+        p = self._ptr
+        rc = self.lib.lsm_buffer_compute_returns(p(self.rewards), p(self.value_preds), p(self.masks), p(self.bad_masks),
+                                                 p(nv), p(den), p(self.returns), self.T, env.num_envs * env.N,
+                                                 C.byref(cfg), env._stream())
+        if rc != 0:
+            raise BufferError(self.lib.lsm_returns_last_error().decode())
+
+    def advantages(self, value_normalizer=None):
+        """The head of GR_MAPPO.train (graph_mappo.py:258-268): returns[:-1] - denormalize(value_preds[:-1]),
+        normalised by the mean and std over entries whose active_masks is non-zero. Returns (advantages
+        [T, n, N, 1] float32, stats float64 [3] = mean, std, active count), device tensors; the
+        statistics are float64 sums in a fixed order. Stream-ordered; no synchronisation with a device
+        normaliser (see _denorm for host-side ones)."""
+        import torch
+        env = self.env
+        count = self.T * env.num_envs * env.N
+        if self._adv_ws is None:
+            nbytes = int(self.lib.lsm_buffer_advantages_workspace_bytes(count))
+            self._adv_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=env.device)
+        ws = self._adv_ws
+        adv = torch.empty((self.T, env.num_envs, env.N, 1), dtype=torch.float32, device=env.device)
+        stats = torch.empty(3, dtype=torch.float64, device=env.device)
+        den = self._denorm(value_normalizer)
+        p = self._ptr
+        rc = self.lib.lsm_buffer_advantages(p(self.returns), p(self.value_preds), p(self.active_masks), p(den), count,
+                                            p(adv), p(stats), p(ws), ws.numel() * 8, env._stream())
+        if rc != 0:
+            raise BufferError(self.lib.lsm_returns_last_error().decode())
+        return adv, stats
+
+    def _gather_sources(self, advantages):
+        """(name, source tensor over rows [0, T) viewed per sample, per-sample shape), in yield order."""
+        E = self.env.E
+        adj_shape = (E, E)
+        src = [("share_obs", self.share_obs), ("obs", self.obs), ("node_obs", self.node_obs), ("adj", self.adj),
+               ("agent_id", self.agent_id), ("share_agent_id", self.share_agent_id),
+               ("value_preds", self.value_preds), ("returns", self.returns), ("masks", self.masks),
+               ("active_masks", self.active_masks), ("advantages", advantages)]
+        return [(k, t, adj_shape if k == "adj" else tuple(t.shape[3:])) for k, t in src]
+
+    def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, indices=None,
+                               generator=None):
+        """GraphReplayBuffer.feed_forward_generator (graph_buffer.py:368-453) for the buffer's fields:
+        yields, per minibatch, a dict of device tensors share_obs, obs, node_obs, adj, agent_id,
+        share_agent_id, value_preds, returns, masks, active_masks, advantages (each [B, ...], row b the
+        sample indices[b] of the field's [:-1].reshape(T * n * N, ...) view) and indices, all gathered by
+        one lsm_buffer_gather launch. adj is always the reference's [B, E, E] matrix; a compact buffer
+        expands it from its table and masks in the same launch. indices: an int64 permutation of the
+        T * n * N samples (validated once, which synchronises); by default torch.randperm on the device
+        (generator: its torch.Generator). The learner gathers its own policy-side tensors (actions,
+        log-probs, rnn states) with the yielded indices.
+
+        The output tensors are allocated once per generator and reused: a yielded batch is valid until
+        the next one is requested."""
+        import torch
+        env = self.env
+        dev = env.device
+        n, N = env.num_envs, env.N
+        batch_size = n * self.T * N
+        if mini_batch_size is None:
+            # the reference's rule (an assert there too): at least one sample per minibatch
+            assert num_mini_batch is not None and batch_size >= num_mini_batch, (
+                "%d minibatches asked of %d samples (%d envs x %d steps x %d agents)"
+                % (num_mini_batch or 0, batch_size, n, self.T, N))
+            mini_batch_size = batch_size // num_mini_batch
+        mb = int(mini_batch_size)
+        if mb < 1:
+            raise BufferError("mini_batch_size < 1")
+        if num_mini_batch is None:
+            num_mini_batch = batch_size // mb
+        if mb * num_mini_batch > batch_size:
+            raise BufferError("mini_batch_size * num_mini_batch exceeds the %d samples" % batch_size)
+        if indices is None:
+            perm = torch.randperm(batch_size, device=dev, generator=generator)
+        else:
+            perm = torch.as_tensor(indices, device=dev)
+            if perm.dtype != torch.int64 or perm.shape != (batch_size,):
+                raise BufferError("indices must be an int64 permutation of the %d samples" % batch_size)
+            perm = perm.contiguous()
+            if not torch.equal(torch.sort(perm).values, torch.arange(batch_size, device=dev)):
+                raise BufferError("indices is not a permutation of range(%d)" % batch_size)
+        plan = self._gather_plan(advantages, mb)
+        for i in range(num_mini_batch):
+            yield self._gather(plan, perm[i * mb:(i + 1) * mb])
+
+    def _gather_plan(self, advantages, mb):
+        """The field descriptors and the output tensors of minibatches of mb samples, built once."""
+        import torch
+        env = self.env
+        dev = env.device
+        batch_size = env.num_envs * self.T * env.N
+        adv = torch.as_tensor(advantages, device=dev)
+        if adv.dtype != torch.float32 or adv.numel() != batch_size:
+            raise BufferError("advantages must be float32 with T * n * N entries")
+        adv = adv.reshape(self.T, env.num_envs, env.N, 1).contiguous()
+        sources = self._gather_sources(adv)
+        out = {k: torch.empty((mb,) + shape, dtype=t.dtype, device=dev) for k, t, shape in sources}
+        fields = (capi.LsmGatherField * len(sources))()
+        for f, (k, t, shape) in zip(fields, sources):
+            f.src, f.dst = t.data_ptr(), out[k].data_ptr()
+            if k == "adj" and self.adj_mask is not None:
+                f.kind, f.masks, f.E, f.N = capi.LSM_GATHER_COMPACT_ADJ, self.adj_mask.data_ptr(), env.E, env.N
+            else:
+                f.kind, f.row_bytes = capi.LSM_GATHER_ROWS, out[k][0].numel() * t.element_size()
+        return fields, out, adv, batch_size
+
+    def _gather(self, plan, idx):
+        """One minibatch: every field's rows idx (a contiguous int64 device tensor) in one launch."""
+        fields, out, _, batch_size = plan   # the plan keeps the advantages tensor alive
+        rc = self.lib.lsm_buffer_gather(fields, len(fields), C.c_void_p(idx.data_ptr()), idx.numel(), batch_size, None,
+                                        self.env._stream())
+        if rc != 0:
+            raise BufferError(self.lib.lsm_gather_last_error().decode())
+        batch = dict(out)
+        batch["indices"] = idx
+        return batch

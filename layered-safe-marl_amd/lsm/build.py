@@ -26,6 +26,9 @@ UNITS = {
     "lsm_edges.hip": [],
     "lsm_buffer.hip": [],
     "lsm_metrics.hip": [],
+    # the learner hand-off (include/lsm_learner.h, a header of its own: not part of build_id())
+    "lsm_returns.hip": ["../../include/lsm_learner.h"],
+    "lsm_gather.hip": ["../../include/lsm_learner.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,4 +1,5 @@
-"""ctypes binding of the C ABI in ``include/lsm_rollout.h`` (``liblsm_rollout.so``).
+"""ctypes binding of the C ABI in ``include/lsm_rollout.h`` and ``include/lsm_learner.h``
+(``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -39,6 +40,12 @@ EXPORTED = ("lsm_create", "lsm_destroy", "lsm_last_error", "lsm_set_value_table"
             "lsm_kernel_name", "lsm_reset_layout", "lsm_layout_doubles", "lsm_host_philox_uniforms",
             "lsm_host_philox4x32", "lsm_episode_summary", "lsm_build_id", "lsm_test_set_mt_stage",
             "lsm_create_select", "lsm_edges_scan_emit", "lsm_test_read_value_bounds", "lsm_kernel_name_for")
+# Every symbol include/lsm_learner.h declares (checked by tests/test_learner_capi.py).
+EXPORTED_LEARNER = ("lsm_buffer_compute_returns", "lsm_host_compute_returns",
+                    "lsm_buffer_advantages_workspace_bytes", "lsm_buffer_advantages", "lsm_returns_last_error",
+                    "lsm_buffer_gather", "lsm_gather_last_error")
+LSM_GATHER_ROWS, LSM_GATHER_COMPACT_ADJ = 0, 1
+LSM_GATHER_MAX_FIELDS = 16
 
 
 class LsmConfig(C.Structure):
@@ -74,6 +81,17 @@ class LsmCurriculum(C.Structure):
         "curriculum_ratio", "sloped", "stair", "ratio_airtaxi", "ratio_scenario",
         "goal_heading_error_thresh", "goal_speed_error_thresh", "min_dist_thresh",
         "separation_distance", "engagement_distance", "world_use_safety_filter", "stair_is_int")]
+
+
+class LsmReturnsConfig(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("gae_lambda", C.c_double), ("use_gae", C.c_int32),
+                ("use_proper_time_limits", C.c_int32)]
+
+
+class LsmGatherField(C.Structure):
+    """lsm_gather_field (include/lsm_learner.h)."""
+    _fields_ = [("kind", C.c_int32), ("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64),
+                ("masks", C.c_void_p), ("E", C.c_int32), ("N", C.c_int32)]
 
 
 class LsmError(RuntimeError):
@@ -133,6 +151,14 @@ def load_library(path: str = LIB_PATH):
         "lsm_build_id": (C.c_char_p, []),
         "lsm_test_set_mt_stage": (I32, [P, I32]),
         "lsm_test_read_value_bounds": (I32, [P, P, I32, P, P]),
+        # include/lsm_learner.h
+        "lsm_buffer_compute_returns": (I32, [P, P, P, P, P, P, P, I32, I64, C.POINTER(LsmReturnsConfig), P]),
+        "lsm_host_compute_returns": (I32, [P, P, P, P, P, P, P, I32, I64, C.POINTER(LsmReturnsConfig)]),
+        "lsm_buffer_advantages_workspace_bytes": (SZ, [I64]),
+        "lsm_buffer_advantages": (I32, [P, P, P, P, I64, P, P, P, SZ, P]),
+        "lsm_returns_last_error": (C.c_char_p, []),
+        "lsm_buffer_gather": (I32, [C.POINTER(LsmGatherField), I32, P, I64, I64, P, P]),
+        "lsm_gather_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
