@@ -193,10 +193,11 @@ def spike_nodes(dyn, shape, bshift):
             "wrap": ((k0, mid1, 0, va, vb), 2, ("below", "above"))}
 
 
-def make_table(dyn, kind, shape, separation=None, bshift=None, seed=7):
+def make_table(dyn, kind, shape, separation=None, bshift=None, seed=7, depth=None):
     """The project's synthetic value table of ``shape`` as HjDataHandle builds it, then ``kind``:
     "smooth" as it is, "rough" plus uniform(+-0.25) noise per node, "spike" with the nodes of
-    spike_nodes(dyn, shape, bshift) lowered by 3.0. Gradients recomputed from the final values."""
+    spike_nodes(dyn, shape, bshift) lowered by 3.0, or by depth[name] for the spikes that the mapping
+    ``depth`` names. Gradients recomputed from the final values."""
     di = dyn == "double_integrator"
     st = hj_tables.synthetic_di_stored(shape) if di else hj_tables.synthetic_airtaxi_stored(shape)
     sep = st["separation_distance"] if separation is None else separation
@@ -205,13 +206,15 @@ def make_table(dyn, kind, shape, separation=None, bshift=None, seed=7):
     if kind == "rough":
         v = (v + np.random.default_rng(seed).uniform(-NOISE, NOISE, v.shape).astype(F32)).astype(F32)
     elif kind == "spike":
-        for node, _, _ in spike_nodes(dyn, shape, bshift).values():
-            v[node] = F32(v[node] - SPIKE_DEPTH)
+        for name, (node, _, _) in spike_nodes(dyn, shape, bshift).items():
+            v[node] = F32(v[node] - F32((depth or {}).get(name, SPIKE_DEPTH)))
     else:
         assert kind == "smooth", kind
     t.values_hj = v
     t.grads_hj = hj_tables.grad_values(v, t.lo, t.hi, t.shape, t.periodic)
     t.extra["kind"] = kind
+    if depth:
+        t.extra["depth"] = tuple(sorted(depth.items()))
     return t
 
 
@@ -330,7 +333,7 @@ def spike_injections(dyn, table, bshift, N):
     "below" pair, that mutant bounds prune it ("no_wrap" preferred for the wrap spike, else
     "no_shared"). flips: mutant -> the argmin the pruned search would return with that mutant's bounds.
     A ladder without such a rung returns the last rung; the caller's assertions then fail."""
-    key = (dyn, tuple(table.shape), bshift, N)
+    key = (dyn, tuple(table.shape), bshift, N, table.extra.get("depth"))
     if key in _SPIKE_CACHE:
         return _SPIKE_CACHE[key]
     good = block_bounds(table.values_hj, table.periodic, bshift)
