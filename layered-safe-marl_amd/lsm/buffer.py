@@ -11,13 +11,21 @@ env's output slots are ring-bound to the buffer (``lsm_bind_output_ring``), one 
 buffer row, so selecting a row is a host-side pointer choice. With a centralized critic
 (``use_centralized_V``, the reference default) the kernel also writes that row's share_obs, masks and
 active_masks (optional output slots); otherwise ``lsm_buffer_insert`` (HIP) derives them from the
-step's obs and dones. agent_id / share_agent_id rows are constant and filled once. Policy-side fields (rnn states, actions, log-probs) stay with the learner.
+step's obs and dones. agent_id / share_agent_id rows are constant and filled once.
+
+With ``policy_rows`` the buffer also keeps the policy-side fields (``graph_buffer.py:117-151``:
+rnn_states, rnn_states_critic, actions, action_log_probs, available_actions): ``insert_step(policy=...)``
+writes a step's rows with one ``lsm_buffer_copy_rows`` launch after the step, zeroing the recurrent
+states of agents that are done (``graph_mpe_runner.py:449-456``), and ``after_update`` carries row T to
+row 0. Without it (the default) those fields stay with the learner.
 
 Between the last env step and the first ppo_update the buffer also does what the reference does with
 it (``include/lsm_learner.h``): ``compute_returns`` (``graph_buffer.py:285-366``, ``csrc/lsm_returns.hip``),
 ``advantages`` (``graph_mappo.py:258-268``) and ``feed_forward_generator`` (``graph_buffer.py:368-453``,
 one ``lsm_buffer_gather`` launch per minibatch, ``csrc/lsm_gather.hip``), on ``value_preds`` handed to
-``insert_step``.
+``insert_step``. For the reference's default, a recurrent policy, ``recurrent_generator``
+(``graph_buffer.py:597-755``) delivers each minibatch of data chunks with one
+``lsm_buffer_gather_chunks`` launch (``include/lsm_recurrent.h``, ``csrc/lsm_chunks.hip``).
 """
 from __future__ import annotations
 
@@ -30,8 +38,19 @@ class BufferError(RuntimeError):
     pass
 
 
+def chunk_rows(chunks, L, T, M):
+    """Flat buffer rows (t * M + column) of a recurrent minibatch, in its time-major order: entry
+    l * C + b is step l of chunk chunks[b], i.e. sample f = chunks[b] * L + l of the reference's
+    (env, agent, t)-ordered view, at row (f % T) * M + f // T. Torch ops on the chunks' device: a learner
+    that keeps its own [T, M, ...] tensors indexes them with these rows (the recurrent states with the
+    first C of them)."""
+    import torch
+    f = chunks.reshape(1, -1) * L + torch.arange(L, device=chunks.device, dtype=chunks.dtype).reshape(-1, 1)
+    return ((f % T) * M + torch.div(f, T, rounding_mode="floor")).reshape(-1)
+
+
 class DeviceGraphBuffer:
-    def __init__(self, env, episode_length=None, use_centralized_V: bool = True):
+    def __init__(self, env, episode_length=None, use_centralized_V: bool = True, policy_rows=None):
         import torch
         if env.return_numpy:
             # ring-bound outputs are never written to the env's own tensors: host copies of them
@@ -65,6 +84,25 @@ class DeviceGraphBuffer:
         self.value_preds = torch.zeros((T1, n, N, 1), dtype=f32, device=dev)
         self.returns = torch.zeros_like(self.value_preds)
         self._adv_ws = None   # advantages(): the partial-sum workspace, allocated on first use
+        # policy-side rows (graph_buffer.py:117-151), only when asked for
+        self.policy_rows = None
+        self.rnn_states = self.rnn_states_critic = self.actions = self.action_log_probs = None
+        self.available_actions = None
+        if policy_rows is not None:
+            pr = dict(recurrent_N=1, act_dim=1, num_actions=None)
+            pr.update(policy_rows)
+            if set(pr) != {"hidden_size", "recurrent_N", "act_dim", "num_actions"}:
+                raise BufferError("policy_rows takes hidden_size, recurrent_N, act_dim and num_actions")
+            hid, rn, ad = int(pr["hidden_size"]), int(pr["recurrent_N"]), int(pr["act_dim"])
+            if hid < 1 or rn < 1 or ad < 1 or (pr["num_actions"] is not None and int(pr["num_actions"]) < 1):
+                raise BufferError("policy_rows sizes must be positive")
+            self.policy_rows = pr
+            self.rnn_states = torch.zeros((T1, n, N, rn, hid), dtype=f32, device=dev)
+            self.rnn_states_critic = torch.zeros_like(self.rnn_states)
+            self.actions = torch.zeros((self.T, n, N, ad), dtype=f32, device=dev)
+            self.action_log_probs = torch.zeros_like(self.actions)
+            if pr["num_actions"] is not None:
+                self.available_actions = torch.ones((T1, n, N, int(pr["num_actions"])), dtype=f32, device=dev)
         self.step = 0
         # agent ids are the same every row (the env returns agent index j for agent j)
         ids = torch.arange(N, dtype=i32, device=dev)
@@ -123,29 +161,78 @@ class DeviceGraphBuffer:
         self.step = 0
         return ep
 
-    def insert_step(self, actions, num_current_episode=None, value_preds=None):
+    def insert_step(self, actions, num_current_episode=None, value_preds=None, policy=None):
         """env.step + GMPERunner.insert's env-side rows for buffer step t = self.step: obs,
         node_obs, adj, share_obs, agent_id, share_agent_id, masks, active_masks at t+1 and
         rewards at t. value_preds (the critic's values for step t, n * N floats), when given, is
-        copied into value_preds[t] first. Returns (dones [n, N] u8, (info, reset_flag, ep_info))
-        device tensors."""
+        copied into value_preds[t] first.
+
+        policy (needs policy_rows): a mapping of device tensors actions, action_log_probs, rnn_states,
+        rnn_states_critic and, with num_actions, optionally available_actions, shaped as one buffer
+        row. They are written by one lsm_buffer_copy_rows launch after the step (GMPERunner.insert +
+        GraphReplayBuffer.insert, graph_mpe_runner.py:444-487, graph_buffer.py:229-249): actions,
+        action_log_probs (and value_preds) into row t, the recurrent states, zeroed where the step's
+        dones are set, and available_actions into row t+1.
+
+        Returns (dones [n, N] u8, (info, reset_flag, ep_info)) device tensors."""
         t = self.step
-        if value_preds is not None:
+        copies = self._policy_copies(t, policy, value_preds) if policy is not None else None
+        if value_preds is not None and copies is None:
             self.value_preds[t].copy_(self._as_f32(value_preds).reshape(self.value_preds[t].shape))
         self._select(t + 1)
         self.env.step_async(actions, num_current_episode)
         self.env.step_wait()
         if not self.fused:
             self._insert(t + 1, True)
+        if copies is not None:
+            arr, keep = copies   # keep: the sources stay referenced until the launch is queued
+            rc = self.lib.lsm_buffer_copy_rows(arr, len(arr), self._done_ptr, self.env.num_envs * self.env.N,
+                                               self.env._stream())
+            if rc != 0:
+                raise BufferError(self.lib.lsm_recurrent_last_error().decode())
         self.step = (t + 1) % self.T
         return self.env.t_done, (self.env.t_info, self.env.t_reset, self.env.t_epinfo)
 
+    def _policy_copies(self, t, policy, value_preds):
+        """The lsm_row_copy descriptors of step t's policy-side rows (and value_preds when given)."""
+        if self.policy_rows is None:
+            raise BufferError("insert_step(policy=...) needs a buffer built with policy_rows")
+        names = {"actions", "action_log_probs", "rnn_states", "rnn_states_critic", "available_actions"}
+        if set(policy) - names:
+            raise BufferError("unknown policy fields: %s" % sorted(set(policy) - names))
+        if names - {"available_actions"} - set(policy):
+            raise BufferError("missing policy fields: %s" % sorted(names - {"available_actions"} - set(policy)))
+        # (source, buffer row, zero where done)
+        plan = [(policy["actions"], self.actions[t], 0), (policy["action_log_probs"], self.action_log_probs[t], 0),
+                (policy["rnn_states"], self.rnn_states[t + 1], 1),
+                (policy["rnn_states_critic"], self.rnn_states_critic[t + 1], 1)]
+        if policy.get("available_actions") is not None:
+            if self.available_actions is None:
+                raise BufferError("available_actions given to a buffer built without num_actions")
+            plan.append((policy["available_actions"], self.available_actions[t + 1], 0))
+        if value_preds is not None:
+            plan.append((value_preds, self.value_preds[t], 0))
+        M = self.env.num_envs * self.env.N
+        arr = (capi.LsmRowCopy * len(plan))()
+        keep = []
+        for c, (src, dst, zero) in zip(arr, plan):
+            s = self._as_f32(src).contiguous()
+            if s.numel() != dst.numel():
+                raise BufferError("a policy tensor has %d elements, its buffer row %d" % (s.numel(), dst.numel()))
+            keep.append(s)
+            c.src, c.dst, c.row_bytes, c.zero_on_done = s.data_ptr(), dst.data_ptr(), dst.numel() // M * 4, zero
+        return arr, keep
+
     def after_update(self):
-        """GraphReplayBuffer.after_update (graph_buffer.py:253-283), env-side fields."""
+        """GraphReplayBuffer.after_update (graph_buffer.py:253-283)."""
         fields = [self.share_obs, self.obs, self.node_obs, self.adj, self.agent_id, self.share_agent_id,
                   self.masks, self.active_masks, self.bad_masks]
         if self.adj_mask is not None:
             fields.append(self.adj_mask)
+        if self.policy_rows is not None:
+            fields += [self.rnn_states, self.rnn_states_critic]
+            if self.available_actions is not None:
+                fields.append(self.available_actions)
         for f in fields:
             f[0].copy_(f[-1])
 
@@ -308,4 +395,101 @@ class DeviceGraphBuffer:
             raise BufferError(self.lib.lsm_gather_last_error().decode())
         batch = dict(out)
         batch["indices"] = idx
+        return batch
+
+    # ---- recurrent policy (include/lsm_recurrent.h) ----------------------------------------------
+
+    def _chunk_sources(self, advantages):
+        """(name, source tensor, per-sample shape), in the reference's yield order
+        (graph_buffer.py:751-755); the policy-side fields only with policy_rows."""
+        E = self.env.E
+        src = [("share_obs", self.share_obs), ("obs", self.obs), ("node_obs", self.node_obs), ("adj", self.adj),
+               ("agent_id", self.agent_id), ("share_agent_id", self.share_agent_id),
+               ("rnn_states", self.rnn_states), ("rnn_states_critic", self.rnn_states_critic),
+               ("actions", self.actions), ("value_preds", self.value_preds), ("returns", self.returns),
+               ("masks", self.masks), ("active_masks", self.active_masks),
+               ("action_log_probs", self.action_log_probs), ("advantages", advantages),
+               ("available_actions", self.available_actions)]
+        return [(k, t, (E, E) if k == "adj" else tuple(t.shape[3:])) for k, t in src if t is not None]
+
+    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, chunks=None, generator=None):
+        """GraphReplayBuffer.recurrent_generator (graph_buffer.py:597-755): the T * n * N samples, ordered
+        (env, agent, t), are cut into data_chunks = T * n * N // data_chunk_length chunks of L consecutive
+        samples (the tail is dropped; when L does not divide T a chunk runs into the next agent's series,
+        as in the reference), and each minibatch takes C = data_chunks // num_mini_batch of them. Yields,
+        per minibatch, a dict of device tensors under the reference's names and in its order: share_obs,
+        obs, node_obs, adj, agent_id, share_agent_id, rnn_states, rnn_states_critic, actions, value_preds,
+        returns, masks, active_masks, action_log_probs, advantages, available_actions (None without
+        num_actions), and chunks. Each is [L * C, ...], row l * C + b step l of chunk chunks[b]; the two
+        recurrent states are [C, recurrent_N, hidden], taken at each chunk's first step. All of it is
+        gathered by one lsm_buffer_gather_chunks launch; adj is always the reference's [L * C, E, E]
+        matrix, which a compact buffer expands in the same launch. A buffer without policy_rows leaves
+        the five policy-side fields out: the learner indexes its own tensors with chunk_rows().
+
+        chunks: an int64 permutation of range(data_chunks) (validated once, which synchronises); by
+        default torch.randperm on the device (generator: its torch.Generator).
+
+        The output tensors are allocated once per generator and reused: a yielded batch is valid until
+        the next one is requested."""
+        import torch
+        env = self.env
+        dev = env.device
+        L = int(data_chunk_length)
+        batch_size = env.num_envs * self.T * env.N
+        if L < 1 or L > batch_size:
+            raise BufferError("data_chunk_length outside 1..%d" % batch_size)
+        data_chunks = batch_size // L
+        mb = data_chunks // int(num_mini_batch)
+        if mb < 1:
+            raise BufferError("%d minibatches asked of %d chunks" % (num_mini_batch, data_chunks))
+        if chunks is None:
+            perm = torch.randperm(data_chunks, device=dev, generator=generator)
+        else:
+            perm = torch.as_tensor(chunks, device=dev)
+            if perm.dtype != torch.int64 or perm.shape != (data_chunks,):
+                raise BufferError("chunks must be an int64 permutation of the %d chunks" % data_chunks)
+            perm = perm.contiguous()
+            if not torch.equal(torch.sort(perm).values, torch.arange(data_chunks, device=dev)):
+                raise BufferError("chunks is not a permutation of range(%d)" % data_chunks)
+        plan = self._chunk_plan(advantages, mb, L)
+        for i in range(int(num_mini_batch)):
+            yield self._gather_chunks(plan, perm[i * mb:(i + 1) * mb])
+
+    def _chunk_plan(self, advantages, mb, L):
+        """The field descriptors and the output tensors of minibatches of mb chunks of L steps, built once."""
+        import torch
+        env = self.env
+        dev = env.device
+        batch_size = env.num_envs * self.T * env.N
+        adv = torch.as_tensor(advantages, device=dev)
+        if adv.dtype != torch.float32 or adv.numel() != batch_size:
+            raise BufferError("advantages must be float32 with T * n * N entries")
+        adv = adv.reshape(self.T, env.num_envs, env.N, 1).contiguous()
+        sources = self._chunk_sources(adv)
+        first = ("rnn_states", "rnn_states_critic")
+        out = {k: torch.empty(((mb if k in first else L * mb),) + shape, dtype=t.dtype, device=dev)
+               for k, t, shape in sources}
+        fields = (capi.LsmChunkField * len(sources))()
+        for f, (k, t, shape) in zip(fields, sources):
+            f.src, f.dst = t.data_ptr(), out[k].data_ptr()
+            if k == "adj" and self.adj_mask is not None:
+                f.kind, f.masks, f.E, f.N = capi.LSM_CHUNK_COMPACT_ADJ, self.adj_mask.data_ptr(), env.E, env.N
+            else:
+                f.kind = capi.LSM_CHUNK_FIRST_ROW if k in first else capi.LSM_CHUNK_ROWS
+                f.row_bytes = out[k][0].numel() * t.element_size()
+        names = [k for k, _, _ in sources]
+        if self.policy_rows is not None and self.available_actions is None:
+            names.append("available_actions")   # the reference yields None for a non-discrete action space
+        return fields, out, adv, names, L
+
+    def _gather_chunks(self, plan, idx):
+        """One minibatch: every field's chunks idx (a contiguous int64 device tensor) in one launch."""
+        fields, out, _, names, L = plan   # the plan keeps the advantages tensor alive
+        env = self.env
+        rc = self.lib.lsm_buffer_gather_chunks(fields, len(fields), C.c_void_p(idx.data_ptr()), idx.numel(), L, self.T,
+                                               env.num_envs * env.N, None, env._stream())
+        if rc != 0:
+            raise BufferError(self.lib.lsm_recurrent_last_error().decode())
+        batch = {k: out.get(k) for k in names}
+        batch["chunks"] = idx
         return batch

@@ -29,6 +29,8 @@ UNITS = {
     # the learner hand-off (include/lsm_learner.h, a header of its own: not part of build_id())
     "lsm_returns.hip": ["../../include/lsm_learner.h"],
     "lsm_gather.hip": ["../../include/lsm_learner.h"],
+    # the recurrent-policy hand-off (include/lsm_recurrent.h, likewise outside build_id())
+    "lsm_chunks.hip": ["../../include/lsm_recurrent.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in ``include/lsm_rollout.h`` and ``include/lsm_learner.h``
-(``liblsm_rollout.so``).
+"""ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h`` and
+``include/lsm_recurrent.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -46,6 +46,12 @@ EXPORTED_LEARNER = ("lsm_buffer_compute_returns", "lsm_host_compute_returns",
                     "lsm_buffer_gather", "lsm_gather_last_error")
 LSM_GATHER_ROWS, LSM_GATHER_COMPACT_ADJ = 0, 1
 LSM_GATHER_MAX_FIELDS = 16
+# Every symbol include/lsm_recurrent.h declares (checked by tests/test_recurrent_capi.py).
+EXPORTED_RECURRENT = ("lsm_buffer_gather_chunks", "lsm_host_gather_chunks", "lsm_buffer_copy_rows",
+                      "lsm_recurrent_last_error")
+LSM_CHUNK_ROWS, LSM_CHUNK_COMPACT_ADJ, LSM_CHUNK_FIRST_ROW = 0, 1, 2
+LSM_CHUNK_MAX_FIELDS = 16
+LSM_COPY_MAX = 8
 
 
 class LsmConfig(C.Structure):
@@ -92,6 +98,17 @@ class LsmGatherField(C.Structure):
     """lsm_gather_field (include/lsm_learner.h)."""
     _fields_ = [("kind", C.c_int32), ("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64),
                 ("masks", C.c_void_p), ("E", C.c_int32), ("N", C.c_int32)]
+
+
+class LsmChunkField(C.Structure):
+    """lsm_chunk_field (include/lsm_recurrent.h)."""
+    _fields_ = [("kind", C.c_int32), ("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64),
+                ("masks", C.c_void_p), ("E", C.c_int32), ("N", C.c_int32)]
+
+
+class LsmRowCopy(C.Structure):
+    """lsm_row_copy (include/lsm_recurrent.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("zero_on_done", C.c_int32)]
 
 
 class LsmError(RuntimeError):
@@ -159,6 +176,11 @@ def load_library(path: str = LIB_PATH):
         "lsm_returns_last_error": (C.c_char_p, []),
         "lsm_buffer_gather": (I32, [C.POINTER(LsmGatherField), I32, P, I64, I64, P, P]),
         "lsm_gather_last_error": (C.c_char_p, []),
+        # include/lsm_recurrent.h
+        "lsm_buffer_gather_chunks": (I32, [C.POINTER(LsmChunkField), I32, P, I64, I64, I64, I64, P, P]),
+        "lsm_host_gather_chunks": (I32, [C.POINTER(LsmChunkField), I32, P, I64, I64, I64, I64, P]),
+        "lsm_buffer_copy_rows": (I32, [C.POINTER(LsmRowCopy), I32, P, I64, P]),
+        "lsm_recurrent_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
