@@ -25,7 +25,9 @@ it (``include/lsm_learner.h``): ``compute_returns`` (``graph_buffer.py:285-366``
 one ``lsm_buffer_gather`` launch per minibatch, ``csrc/lsm_gather.hip``), on ``value_preds`` handed to
 ``insert_step``. For the reference's default, a recurrent policy, ``recurrent_generator``
 (``graph_buffer.py:597-755``) delivers each minibatch of data chunks with one
-``lsm_buffer_gather_chunks`` launch (``include/lsm_recurrent.h``, ``csrc/lsm_chunks.hip``).
+``lsm_buffer_gather_chunks`` launch (``include/lsm_recurrent.h``, ``csrc/lsm_chunks.hip``). With
+``edges=True`` both generators deliver the minibatch as the GNN consumes it: ``adj`` stays in the buffer and
+the batch carries ``edge_index`` / ``edge_attr`` (``include/lsm_minibatch_edges.h``, ``csrc/lsm_mb_edges.hip``).
 """
 from __future__ import annotations
 
@@ -321,7 +323,7 @@ class DeviceGraphBuffer:
         return [(k, t, adj_shape if k == "adj" else tuple(t.shape[3:])) for k, t in src]
 
     def feed_forward_generator(self, advantages, num_mini_batch=None, mini_batch_size=None, indices=None,
-                               generator=None):
+                               generator=None, edges=False):
         """GraphReplayBuffer.feed_forward_generator (graph_buffer.py:368-453) for the buffer's fields:
         yields, per minibatch, a dict of device tensors share_obs, obs, node_obs, adj, agent_id,
         share_agent_id, value_preds, returns, masks, active_masks, advantages (each [B, ...], row b the
@@ -331,6 +333,12 @@ class DeviceGraphBuffer:
         T * n * N samples (validated once, which synchronises); by default torch.randperm on the device
         (generator: its torch.Generator). The learner gathers its own policy-side tensors (actions,
         log-probs, rnn states) with the yielded indices.
+
+        edges=True: the minibatch comes as the GNN consumes it (GNNBase.forward, gnn.py:545-564, keeps
+        only process_adj's result). adj is left out of the gather launch and yielded as None, and the
+        batch ends with edge_index int64 [2, nnz] and edge_attr float32 [nnz, 1], process_adj of the
+        minibatch's [B, E, E] adjacency, made from the buffer's own adjacency in either layout by
+        lsm.edges.minibatch_edges (which synchronises once, like torch.nonzero); they are fresh tensors.
 
         The output tensors are allocated once per generator and reused: a yielded batch is valid until
         the next one is requested."""
@@ -361,11 +369,11 @@ class DeviceGraphBuffer:
             perm = perm.contiguous()
             if not torch.equal(torch.sort(perm).values, torch.arange(batch_size, device=dev)):
                 raise BufferError("indices is not a permutation of range(%d)" % batch_size)
-        plan = self._gather_plan(advantages, mb)
+        plan = self._gather_plan(advantages, mb, edges)
         for i in range(num_mini_batch):
             yield self._gather(plan, perm[i * mb:(i + 1) * mb])
 
-    def _gather_plan(self, advantages, mb):
+    def _gather_plan(self, advantages, mb, edges=False):
         """The field descriptors and the output tensors of minibatches of mb samples, built once."""
         import torch
         env = self.env
@@ -376,6 +384,9 @@ class DeviceGraphBuffer:
             raise BufferError("advantages must be float32 with T * n * N entries")
         adv = adv.reshape(self.T, env.num_envs, env.N, 1).contiguous()
         sources = self._gather_sources(adv)
+        names = [k for k, _, _ in sources]
+        if edges:   # adj stays in the buffer: _minibatch_edges reads it there
+            sources = [s for s in sources if s[0] != "adj"]
         out = {k: torch.empty((mb,) + shape, dtype=t.dtype, device=dev) for k, t, shape in sources}
         fields = (capi.LsmGatherField * len(sources))()
         for f, (k, t, shape) in zip(fields, sources):
@@ -384,18 +395,26 @@ class DeviceGraphBuffer:
                 f.kind, f.masks, f.E, f.N = capi.LSM_GATHER_COMPACT_ADJ, self.adj_mask.data_ptr(), env.E, env.N
             else:
                 f.kind, f.row_bytes = capi.LSM_GATHER_ROWS, out[k][0].numel() * t.element_size()
-        return fields, out, adv, batch_size
+        return fields, out, adv, batch_size, names, bool(edges)
 
     def _gather(self, plan, idx):
         """One minibatch: every field's rows idx (a contiguous int64 device tensor) in one launch."""
-        fields, out, _, batch_size = plan   # the plan keeps the advantages tensor alive
+        fields, out, _, batch_size, names, edges = plan   # the plan keeps the advantages tensor alive
         rc = self.lib.lsm_buffer_gather(fields, len(fields), C.c_void_p(idx.data_ptr()), idx.numel(), batch_size, None,
                                         self.env._stream())
         if rc != 0:
             raise BufferError(self.lib.lsm_gather_last_error().decode())
-        batch = dict(out)
+        batch = {k: out.get(k) for k in names}
         batch["indices"] = idx
+        if edges:
+            batch["edge_index"], batch["edge_attr"] = self._minibatch_edges(idx, None)
         return batch
+
+    def _minibatch_edges(self, ids, chunks):
+        """process_adj of the minibatch named by ids, from rows [0, T) of the buffer's adjacency."""
+        from . import edges as lsm_edges
+        masks = self.adj_mask[:self.T] if self.adj_mask is not None else None
+        return lsm_edges.minibatch_edges(self.adj[:self.T], masks, self.env.N, ids, chunks=chunks)
 
     # ---- recurrent policy (include/lsm_recurrent.h) ----------------------------------------------
 
@@ -412,7 +431,8 @@ class DeviceGraphBuffer:
                ("available_actions", self.available_actions)]
         return [(k, t, (E, E) if k == "adj" else tuple(t.shape[3:])) for k, t in src if t is not None]
 
-    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, chunks=None, generator=None):
+    def recurrent_generator(self, advantages, num_mini_batch, data_chunk_length, chunks=None, generator=None,
+                            edges=False):
         """GraphReplayBuffer.recurrent_generator (graph_buffer.py:597-755): the T * n * N samples, ordered
         (env, agent, t), are cut into data_chunks = T * n * N // data_chunk_length chunks of L consecutive
         samples (the tail is dropped; when L does not divide T a chunk runs into the next agent's series,
@@ -428,6 +448,11 @@ class DeviceGraphBuffer:
 
         chunks: an int64 permutation of range(data_chunks) (validated once, which synchronises); by
         default torch.randperm on the device (generator: its torch.Generator).
+
+        edges=True: as in feed_forward_generator -- adj is left out of the gather launch and yielded as
+        None, and the batch ends with edge_index / edge_attr, process_adj of the minibatch's
+        [L * C, E, E] adjacency (graph l * C + b is step l of chunk chunks[b]), fresh tensors made from
+        the buffer's own adjacency by lsm.edges.minibatch_edges.
 
         The output tensors are allocated once per generator and reused: a yielded batch is valid until
         the next one is requested."""
@@ -451,11 +476,11 @@ class DeviceGraphBuffer:
             perm = perm.contiguous()
             if not torch.equal(torch.sort(perm).values, torch.arange(data_chunks, device=dev)):
                 raise BufferError("chunks is not a permutation of range(%d)" % data_chunks)
-        plan = self._chunk_plan(advantages, mb, L)
+        plan = self._chunk_plan(advantages, mb, L, edges)
         for i in range(int(num_mini_batch)):
             yield self._gather_chunks(plan, perm[i * mb:(i + 1) * mb])
 
-    def _chunk_plan(self, advantages, mb, L):
+    def _chunk_plan(self, advantages, mb, L, edges=False):
         """The field descriptors and the output tensors of minibatches of mb chunks of L steps, built once."""
         import torch
         env = self.env
@@ -466,6 +491,9 @@ class DeviceGraphBuffer:
             raise BufferError("advantages must be float32 with T * n * N entries")
         adv = adv.reshape(self.T, env.num_envs, env.N, 1).contiguous()
         sources = self._chunk_sources(adv)
+        names = [k for k, _, _ in sources]
+        if edges:   # adj stays in the buffer: _minibatch_edges reads it there
+            sources = [s for s in sources if s[0] != "adj"]
         first = ("rnn_states", "rnn_states_critic")
         out = {k: torch.empty(((mb if k in first else L * mb),) + shape, dtype=t.dtype, device=dev)
                for k, t, shape in sources}
@@ -477,14 +505,13 @@ class DeviceGraphBuffer:
             else:
                 f.kind = capi.LSM_CHUNK_FIRST_ROW if k in first else capi.LSM_CHUNK_ROWS
                 f.row_bytes = out[k][0].numel() * t.element_size()
-        names = [k for k, _, _ in sources]
         if self.policy_rows is not None and self.available_actions is None:
             names.append("available_actions")   # the reference yields None for a non-discrete action space
-        return fields, out, adv, names, L
+        return fields, out, adv, names, L, bool(edges)
 
     def _gather_chunks(self, plan, idx):
         """One minibatch: every field's chunks idx (a contiguous int64 device tensor) in one launch."""
-        fields, out, _, names, L = plan   # the plan keeps the advantages tensor alive
+        fields, out, _, names, L, edges = plan   # the plan keeps the advantages tensor alive
         env = self.env
         rc = self.lib.lsm_buffer_gather_chunks(fields, len(fields), C.c_void_p(idx.data_ptr()), idx.numel(), L, self.T,
                                                env.num_envs * env.N, None, env._stream())
@@ -492,4 +519,6 @@ class DeviceGraphBuffer:
             raise BufferError(self.lib.lsm_recurrent_last_error().decode())
         batch = {k: out.get(k) for k in names}
         batch["chunks"] = idx
+        if edges:
+            batch["edge_index"], batch["edge_attr"] = self._minibatch_edges(idx, (L, self.T, env.num_envs * env.N))
         return batch

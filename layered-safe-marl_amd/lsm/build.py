@@ -31,6 +31,8 @@ UNITS = {
     "lsm_gather.hip": ["../../include/lsm_learner.h"],
     # the recurrent-policy hand-off (include/lsm_recurrent.h, likewise outside build_id())
     "lsm_chunks.hip": ["../../include/lsm_recurrent.h"],
+    # minibatch edge lists from the buffer (include/lsm_minibatch_edges.h, likewise outside build_id())
+    "lsm_mb_edges.hip": ["../../include/lsm_minibatch_edges.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,5 +1,5 @@
-"""ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h`` and
-``include/lsm_recurrent.h`` (``liblsm_rollout.so``).
+"""ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
+``include/lsm_recurrent.h`` and ``include/lsm_minibatch_edges.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -52,6 +52,10 @@ EXPORTED_RECURRENT = ("lsm_buffer_gather_chunks", "lsm_host_gather_chunks", "lsm
 LSM_CHUNK_ROWS, LSM_CHUNK_COMPACT_ADJ, LSM_CHUNK_FIRST_ROW = 0, 1, 2
 LSM_CHUNK_MAX_FIELDS = 16
 LSM_COPY_MAX = 8
+# Every symbol include/lsm_minibatch_edges.h declares (checked by tests/test_mb_edges_capi.py).
+EXPORTED_MB_EDGES = ("lsm_mb_edges_workspace_bytes", "lsm_mb_edges_count", "lsm_mb_edges_emit", "lsm_host_mb_edges",
+                     "lsm_mb_edges_last_error")
+LSM_MB_INDICES, LSM_MB_CHUNKS = 0, 1
 
 
 class LsmConfig(C.Structure):
@@ -109,6 +113,13 @@ class LsmChunkField(C.Structure):
 class LsmRowCopy(C.Structure):
     """lsm_row_copy (include/lsm_recurrent.h)."""
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("zero_on_done", C.c_int32)]
+
+
+class LsmMbGraphs(C.Structure):
+    """lsm_mb_graphs (include/lsm_minibatch_edges.h), passed by value."""
+    _fields_ = [("adj", C.c_void_p), ("masks", C.c_void_p), ("E", C.c_int32), ("N", C.c_int32), ("rows", C.c_int64),
+                ("kind", C.c_int32), ("ids", C.c_void_p), ("count", C.c_int64), ("L", C.c_int64), ("T", C.c_int64),
+                ("M", C.c_int64)]
 
 
 class LsmError(RuntimeError):
@@ -181,6 +192,12 @@ def load_library(path: str = LIB_PATH):
         "lsm_host_gather_chunks": (I32, [C.POINTER(LsmChunkField), I32, P, I64, I64, I64, I64, P]),
         "lsm_buffer_copy_rows": (I32, [C.POINTER(LsmRowCopy), I32, P, I64, P]),
         "lsm_recurrent_last_error": (C.c_char_p, []),
+        # include/lsm_minibatch_edges.h
+        "lsm_mb_edges_workspace_bytes": (SZ, [I64]),
+        "lsm_mb_edges_count": (I32, [LsmMbGraphs, P, P, SZ, P, P]),
+        "lsm_mb_edges_emit": (I32, [LsmMbGraphs, P, I64, I64, P, P, P]),
+        "lsm_host_mb_edges": (I32, [LsmMbGraphs, I64, P, P, P, P]),
+        "lsm_mb_edges_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

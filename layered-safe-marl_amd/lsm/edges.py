@@ -14,6 +14,10 @@ edges), else between them. ``counts`` (int64 [B], the step kernel's LSM_OUT_ADJ_
 adjacency) skips the count pass: the call is then a scan and one emit pass over the adjacency
 (``lsm_edges_scan_emit``), and a count that does not match its graph raises. All work runs in
 ``lsm_edges.hip`` through the C ABI; there is no torch/CPU fallback.
+
+``minibatch_edges(buffer_adj, masks, N, ids, chunks=None)`` is ``process_adj`` of a PPO minibatch named
+by sample or chunk ids into a replay buffer's adjacency (either layout), without the dense minibatch
+(``lsm_mb_edges.hip``); ``DeviceGraphBuffer``'s generators call it with ``edges=True``.
 """
 from __future__ import annotations
 
@@ -121,6 +125,114 @@ def _run(adj, masks, B, E, N, counts=None):
     if nnz:
         _check(lib.lsm_edges_emit(ap, mp, B, E, N, C.c_void_p(offsets.data_ptr()), nnz,
                                   C.c_void_p(edge_index.data_ptr()), C.c_void_p(edge_attr.data_ptr()), stream), lib)
+    return edge_index, edge_attr
+
+
+def _mb_check(rc, lib):
+    if rc != 0:
+        raise EdgeError(lib.lsm_mb_edges_last_error().decode())
+
+
+# offsets (+ the bad-id word, cleared here and after every report) and workspace of the last few
+# (device, stream, G) of minibatch_edges, reused like _SCRATCH
+_MB_SCRATCH = {}
+
+
+def _mb_scratch(lib, dev, stream_handle, G):
+    torch = _torch()
+    key = (dev.index, stream_handle, G)
+    hit = _MB_SCRATCH.get(key)
+    if hit is None:
+        ws_bytes = int(lib.lsm_mb_edges_workspace_bytes(G))
+        hit = (torch.zeros(G + 2, dtype=torch.int64, device=dev),   # offsets[G + 1]: the bad-id word
+               torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev), ws_bytes)
+        if len(_MB_SCRATCH) >= 8:
+            _MB_SCRATCH.clear()
+        _MB_SCRATCH[key] = hit
+    return hit
+
+
+def minibatch_edges(buffer_adj, masks, N, ids, *, chunks=None):
+    """``process_adj`` of a minibatch whose graphs are named by ids into a replay buffer's sample rows
+    (``include/lsm_minibatch_edges.h``, ``csrc/lsm_mb_edges.hip``); the dense ``[G, E, E]`` minibatch is
+    not built.
+
+    ``buffer_adj``: the buffer's adjacency over its ``rows = T * n * N`` sample rows, a contiguous
+    float32 CUDA tensor ``[..., E, E]``: ``rows`` matrices in the reference layout (``masks`` None), or
+    the ``rows / N`` per-env tables of the compact layout with ``masks`` int64 ``[..., ceil(E/64)]``, one
+    row of disconnect words per sample. ``ids`` int64: sample rows (``chunks`` None, the samples of
+    ``feed_forward_generator``; graph g = ``ids[g]``), or chunk ids with ``chunks = (L, T, M)`` (the
+    minibatch of ``recurrent_generator``: graph ``l * len(ids) + b`` is step l of chunk ``ids[b]``).
+    Returns ``(edge_index int64 [2, nnz], edge_attr float32 [nnz, 1])`` with node numbers ``g * E + r``,
+    equal to ``process_adj`` of the gathered minibatch adjacency. An id outside its range raises.
+
+    The call follows ``process_adj``'s policy: one synchronisation, after both kernels when the bound
+    ``G * E * E`` of the outputs fits BOUNDED_OUTPUT_BYTES (results are views of the bounded buffers,
+    copied to exact size below 1 / SHRINK_RATIO of it), else between them."""
+    torch = _torch()
+    lib = capi.load_library()
+    dev = buffer_adj.device
+    if dev.type != "cuda":
+        raise EdgeError("minibatch_edges needs CUDA (HIP) tensors; the edge list is built on the GPU")
+    if buffer_adj.dtype != torch.float32 or buffer_adj.dim() < 3 or buffer_adj.size(-1) != buffer_adj.size(-2):
+        raise EdgeError("buffer_adj must be float32 [..., E, E]")
+    if not buffer_adj.is_contiguous():
+        raise EdgeError("buffer_adj must be contiguous (a slice of leading rows is)")
+    if ids.dtype != torch.int64 or ids.dim() != 1 or ids.device != dev:
+        raise EdgeError("ids must be int64 [count] on the adjacency's device")
+    ids = ids.contiguous()
+    E = buffer_adj.size(-1)
+    graphs = buffer_adj.numel() // (E * E)
+    if masks is None:
+        rows, mp = graphs, None
+    else:
+        W = (E + 63) // 64
+        if masks.dtype != torch.int64 or masks.device != dev or masks.size(-1) != W or not masks.is_contiguous():
+            raise EdgeError("masks must be contiguous int64 [..., ceil(E/64)] on the adjacency's device")
+        rows = masks.numel() // W
+        if N < 1 or rows != graphs * N:
+            raise EdgeError("compact layout: %d mask rows for %d tables of N = %d agents" % (rows, graphs, N))
+        mp = masks.data_ptr()
+    d = capi.LsmMbGraphs(adj=buffer_adj.data_ptr(), masks=mp, E=E, N=int(N), rows=rows, kind=capi.LSM_MB_INDICES,
+                         ids=ids.data_ptr() or None, count=ids.numel())
+    G = ids.numel()
+    if chunks is not None:
+        d.kind = capi.LSM_MB_CHUNKS
+        d.L, d.T, d.M = (int(x) for x in chunks)
+        if d.L < 1:
+            raise EdgeError("chunks: L < 1")
+        G *= d.L
+    if G > 2 ** 31 - 1:
+        raise EdgeError("more than 2^31 - 1 graphs in one call; split the minibatch")
+    sh = torch.cuda.current_stream(dev).cuda_stream
+    stream = C.c_void_p(sh)
+    offsets, ws, ws_bytes = _mb_scratch(lib, dev, sh, G)
+    op = offsets.data_ptr()
+    _mb_check(lib.lsm_mb_edges_count(d, C.c_void_p(op), C.c_void_p(ws.data_ptr()), ws_bytes,
+                                     C.c_void_p(op + 8 * (G + 1)), stream), lib)
+    cap = G * E * E
+
+    def read_nnz():   # the one sync, as in torch.nonzero: offsets[G] and the bad-id word behind it
+        nnz, bad = offsets[G:].tolist()
+        if bad:
+            offsets[G + 1] = 0
+            raise EdgeError("an id is outside the buffer's %s" % ("chunks" if chunks is not None else "sample rows"))
+        if nnz > cap:
+            raise EdgeError("edge count %d exceeds G*E*E = %d" % (nnz, cap))
+        return nnz
+
+    if 0 < cap * 20 <= BOUNDED_OUTPUT_BYTES:
+        ebuf = torch.empty(2 * cap, dtype=torch.int64, device=dev)
+        abuf = torch.empty(cap, dtype=torch.float32, device=dev)
+        _mb_check(lib.lsm_mb_edges_emit(d, C.c_void_p(op), -1, cap, C.c_void_p(ebuf.data_ptr()),
+                                        C.c_void_p(abuf.data_ptr()), stream), lib)
+        return _bounded(ebuf, abuf, read_nnz(), cap)   # after both kernels
+    nnz = read_nnz()
+    edge_index = torch.empty((2, nnz), dtype=torch.int64, device=dev)
+    edge_attr = torch.empty((nnz, 1), dtype=torch.float32, device=dev)
+    if nnz:
+        _mb_check(lib.lsm_mb_edges_emit(d, C.c_void_p(op), nnz, nnz, C.c_void_p(edge_index.data_ptr()),
+                                        C.c_void_p(edge_attr.data_ptr()), stream), lib)
     return edge_index, edge_attr
 
 
