@@ -33,6 +33,8 @@ UNITS = {
     "lsm_chunks.hip": ["../../include/lsm_recurrent.h"],
     # minibatch edge lists from the buffer (include/lsm_minibatch_edges.h, likewise outside build_id())
     "lsm_mb_edges.hip": ["../../include/lsm_minibatch_edges.h"],
+    # the fused graph-encoder forward (include/lsm_gnn.h, likewise outside build_id())
+    "lsm_gnn.hip": ["../../include/lsm_gnn.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,5 +1,6 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
-``include/lsm_recurrent.h`` and ``include/lsm_minibatch_edges.h`` (``liblsm_rollout.so``).
+``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h`` and ``include/lsm_gnn.h``
+(``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -56,6 +57,9 @@ LSM_COPY_MAX = 8
 EXPORTED_MB_EDGES = ("lsm_mb_edges_workspace_bytes", "lsm_mb_edges_count", "lsm_mb_edges_emit", "lsm_host_mb_edges",
                      "lsm_mb_edges_last_error")
 LSM_MB_INDICES, LSM_MB_CHUNKS = 0, 1
+# Every symbol include/lsm_gnn.h declares (checked by tests/test_gnn_capi.py).
+EXPORTED_GNN = ("lsm_gnn_weights_floats", "lsm_gnn_forward", "lsm_host_gnn_forward", "lsm_gnn_last_error")
+LSM_GNN_NODE, LSM_GNN_GLOBAL_MEAN, LSM_GNN_GLOBAL_MAX, LSM_GNN_GLOBAL_ADD = 0, 1, 2, 3
 
 
 class LsmConfig(C.Structure):
@@ -120,6 +124,13 @@ class LsmMbGraphs(C.Structure):
     _fields_ = [("adj", C.c_void_p), ("masks", C.c_void_p), ("E", C.c_int32), ("N", C.c_int32), ("rows", C.c_int64),
                 ("kind", C.c_int32), ("ids", C.c_void_p), ("count", C.c_int64), ("L", C.c_int64), ("T", C.c_int64),
                 ("M", C.c_int64)]
+
+
+class LsmGnnConfig(C.Structure):
+    """lsm_gnn_config (include/lsm_gnn.h), passed by value."""
+    _fields_ = [(n, C.c_int32) for n in ("F", "num_embeddings", "embedding_size", "embed_hidden", "embed_layer_N",
+                                         "embed_relu", "layer_norm", "C", "H", "concat", "layer_N", "relu", "aggr",
+                                         "ego_only")]
 
 
 class LsmError(RuntimeError):
@@ -198,6 +209,11 @@ def load_library(path: str = LIB_PATH):
         "lsm_mb_edges_emit": (I32, [LsmMbGraphs, P, I64, I64, P, P, P]),
         "lsm_host_mb_edges": (I32, [LsmMbGraphs, I64, P, P, P, P]),
         "lsm_mb_edges_last_error": (C.c_char_p, []),
+        # include/lsm_gnn.h
+        "lsm_gnn_weights_floats": (SZ, [LsmGnnConfig]),
+        "lsm_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P, P]),
+        "lsm_host_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P]),
+        "lsm_gnn_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -1,0 +1,260 @@
+"""The reference's graph encoder, ``GNNBase.forward`` (``onpolicy/algorithms/utils/gnn.py:545-564``), as
+one kernel launch on the step's own outputs (``csrc/lsm_gnn.hip`` through ``include/lsm_gnn.h``).
+
+``GraphEncoder.forward(node_obs, adj, agent_id)`` takes what ``GNNBase.forward`` takes (CUDA float32
+``[B, E, F]`` / ``[B, E, E]``, ``agent_id`` ``[B, 1]`` or ``[B]``) and returns its ``[B, out_dim]`` row per
+graph; ``forward_compact`` reads the compact adjacency layout (one ``[n, E, E]`` table + per-ego
+disconnect words) without expanding it. No edge list, no per-edge tensor and no host synchronisation:
+``process_adj`` is not called. Inference only (``GMPERunner.collect``, evaluation); there is no backward
+pass, and no CPU fallback, as elsewhere in the project.
+
+Weights travel as one packed float32 blob (layout: ``include/lsm_gnn.h``). ``pack_weights`` builds it from
+a ``GNNBase`` state dict, checking every shape against the config; ``GraphEncoder.load`` refreshes the
+device copy after an optimiser step.
+
+``embed_add_self_loop`` has no effect in the reference (``EmbedConv.forward`` adds self loops only when
+``edge_attr is None``, which ``GNNBase`` never passes: gnn.py:112), so ``GnnConfig`` has no such field.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import capi
+
+AGGR = {"node": capi.LSM_GNN_NODE, "global_mean": capi.LSM_GNN_GLOBAL_MEAN, "global_max": capi.LSM_GNN_GLOBAL_MAX,
+        "global_add": capi.LSM_GNN_GLOBAL_ADD}
+
+
+class GnnError(RuntimeError):
+    pass
+
+
+def _torch():
+    import torch
+    return torch
+
+
+@dataclass(frozen=True)
+class GnnConfig:
+    """The network's shape: the fields of ``lsm_gnn_config``. ``aggr``: 'node', 'global_mean',
+    'global_max' or 'global_add'. The defaults are the reference's (onpolicy/config.py:400-446)."""
+    F: int
+    num_embeddings: int = 4
+    embedding_size: int = 2
+    embed_hidden: int = 16
+    embed_layer_N: int = 1
+    embed_relu: bool = True
+    layer_norm: bool = True
+    C: int = 16
+    H: int = 3
+    concat: bool = False
+    layer_N: int = 2
+    relu: bool = True
+    aggr: str = "node"
+    ego_only: bool = False   # timing knob of the last layer (include/lsm_gnn.h); same output
+
+    @classmethod
+    def from_args(cls, all_args, node_obs_dim: int, graph_aggr: str) -> "GnnConfig":
+        """From the reference's argument names; graph_aggr is GNNBase's 'node' or 'global' (the latter
+        with all_args.global_aggr_type)."""
+        if graph_aggr == "node":
+            aggr = "node"
+        elif graph_aggr == "global":
+            aggr = "global_%s" % all_args.global_aggr_type
+        else:
+            raise ValueError("graph_aggr must be 'node' or 'global', got %r" % (graph_aggr,))
+        return cls(F=int(node_obs_dim), num_embeddings=int(all_args.num_embeddings),
+                   embedding_size=int(all_args.embedding_size), embed_hidden=int(all_args.embed_hidden_size),
+                   embed_layer_N=int(all_args.embed_layer_N), embed_relu=bool(all_args.embed_use_ReLU),
+                   layer_norm=bool(all_args.use_feature_normalization), C=int(all_args.gnn_hidden_size),
+                   H=int(all_args.gnn_num_heads), concat=bool(all_args.gnn_concat_heads),
+                   layer_N=int(all_args.gnn_layer_N), relu=bool(all_args.gnn_use_ReLU), aggr=aggr)
+
+    @property
+    def out_dim(self) -> int:
+        return self.C * (self.H if self.concat else 1)
+
+    def struct(self) -> capi.LsmGnnConfig:
+        if self.aggr not in AGGR:
+            raise ValueError("aggr must be one of %s, got %r" % (sorted(AGGR), self.aggr))
+        return capi.LsmGnnConfig(F=self.F, num_embeddings=self.num_embeddings, embedding_size=self.embedding_size,
+                                 embed_hidden=self.embed_hidden, embed_layer_N=self.embed_layer_N,
+                                 embed_relu=int(self.embed_relu), layer_norm=int(self.layer_norm), C=self.C, H=self.H,
+                                 concat=int(self.concat), layer_N=self.layer_N, relu=int(self.relu),
+                                 aggr=AGGR[self.aggr], ego_only=int(self.ego_only))
+
+
+def weight_entries(cfg: GnnConfig):
+    """[(state-dict name without prefix, shape)] in the blob's order (include/lsm_gnn.h)."""
+    Hd, HC, D = cfg.embed_hidden, cfg.H * cfg.C, cfg.out_dim
+    K = cfg.F - 1 + cfg.embedding_size + 1
+    out = [("embed_layer.entity_embed.weight", (cfg.num_embeddings, cfg.embedding_size)),
+           ("embed_layer.lin1.weight", (Hd, K)), ("embed_layer.lin1.bias", (Hd,)),
+           ("embed_layer.layer_norm.weight", (Hd,)), ("embed_layer.layer_norm.bias", (Hd,))]
+    for k in range(cfg.embed_layer_N):
+        out += [("embed_layer.layers.%d.weight" % (3 * k), (Hd, Hd)), ("embed_layer.layers.%d.bias" % (3 * k), (Hd,))]
+    for l in range(cfg.layer_N + 1):
+        conv = "gnn1" if l == 0 else "gnn2.%d" % (l - 1)
+        din = Hd if l == 0 else D
+        for lin in ("query", "key", "value"):
+            out += [("%s.lin_%s.weight" % (conv, lin), (HC, din)), ("%s.lin_%s.bias" % (conv, lin), (HC,))]
+        out += [("%s.lin_edge.weight" % conv, (HC, 1)),
+                ("%s.lin_skip.weight" % conv, (D, din)), ("%s.lin_skip.bias" % conv, (D,))]
+    return out
+
+
+def weights_floats(cfg: GnnConfig) -> int:
+    """lsm_gnn_weights_floats(cfg); raises for a config the library refuses."""
+    lib = capi.load_library()
+    n = int(lib.lsm_gnn_weights_floats(cfg.struct()))
+    if n == 0:
+        raise GnnError(lib.lsm_gnn_last_error().decode())
+    return n
+
+
+def pack_weights(state_dict, cfg: GnnConfig, prefix: str = "gnn.") -> np.ndarray:
+    """The packed float32 blob of a GNNBase state dict (tensors or arrays). Every entry's shape is
+    checked against cfg; a missing or mis-shaped one is refused by name. Without layer norm the state
+    dict has no layer_norm entries (nn.Identity) and the blob's unread gamma / beta are 1 / 0."""
+    parts = []
+    for name, shape in weight_entries(cfg):
+        key = prefix + name
+        if key not in state_dict:
+            if ".layer_norm." in name and not cfg.layer_norm:
+                parts.append(np.full(shape, 1.0 if name.endswith("weight") else 0.0, np.float32).reshape(-1))
+                continue
+            raise GnnError("pack_weights: %s is missing from the state dict" % key)
+        v = state_dict[key]
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if tuple(a.shape) != shape:
+            raise GnnError("pack_weights: %s has shape %s, the config needs %s" % (key, tuple(a.shape), shape))
+        parts.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
+    blob = np.concatenate(parts)
+    if blob.size != weights_floats(cfg):
+        raise GnnError("pack_weights: %d floats packed, the library expects %d" % (blob.size, weights_floats(cfg)))
+    return blob
+
+
+def unpack_weights(blob, cfg: GnnConfig, prefix: str = "gnn."):
+    """The inverse of pack_weights: {name: float32 array} (layer_norm entries only with layer norm)."""
+    blob = np.asarray(blob, dtype=np.float32).reshape(-1)
+    if blob.size != weights_floats(cfg):
+        raise GnnError("unpack_weights: blob of %d floats, the config needs %d" % (blob.size, weights_floats(cfg)))
+    out, o = {}, 0
+    for name, shape in weight_entries(cfg):
+        n = int(np.prod(shape))
+        if cfg.layer_norm or ".layer_norm." not in name:
+            out[prefix + name] = blob[o:o + n].reshape(shape).copy()
+        o += n
+    return out
+
+
+class GraphEncoder:
+    """GNNBase.forward on the GPU for one config and one weight blob.
+
+    The output tensor is preallocated per (B, stream) and is valid until the next call with that B on
+    that stream. check=True reads the call's bad-input word (one synchronisation) and raises when an
+    entity type or an agent_id was out of range; by default the word is not read."""
+
+    def __init__(self, cfg: GnnConfig, weights, device):
+        torch = _torch()
+        self.cfg = cfg
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise GnnError("GraphEncoder needs a CUDA (HIP) device; there is no CPU fallback")
+        self.lib = capi.load_library()
+        self._struct = cfg.struct()
+        self._n = weights_floats(cfg)
+        self.weights = torch.empty(self._n, dtype=torch.float32, device=self.device)
+        self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._out = {}
+        self._set(weights)
+
+    def _set(self, blob):
+        torch = _torch()
+        if isinstance(blob, torch.Tensor):
+            src = blob.detach().reshape(-1).to(torch.float32)
+        else:
+            src = torch.from_numpy(np.ascontiguousarray(blob, dtype=np.float32).reshape(-1))
+        if src.numel() != self._n:
+            raise GnnError("weight blob of %d floats, the config needs %d" % (src.numel(), self._n))
+        self.weights.copy_(src, non_blocking=True)   # the one device copy, on the current stream
+
+    def load(self, state_dict, prefix: str = "gnn."):
+        """Refresh the blob from a GNNBase state dict (after each optimiser step)."""
+        self._set(pack_weights(state_dict, self.cfg, prefix))
+
+    def _tensor(self, t, name, dtype, shape):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise GnnError("%s must be a CUDA (HIP) tensor; there is no CPU fallback" % name)
+        if t.device != self.device:
+            raise GnnError("%s is on %s, the encoder on %s" % (name, t.device, self.device))
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+            raise GnnError("%s must be %s %s, got %s %s" % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+        return t if t.is_contiguous() else t.contiguous()
+
+    def _run(self, node_obs, adj, masks, B, E, N, agent_id, check):
+        torch = _torch()
+        cfg = self.cfg
+        node_obs = self._tensor(node_obs, "node_obs", torch.float32, (B, E, cfg.F))
+        aid = None
+        if cfg.aggr == "node":
+            if agent_id is None:
+                raise GnnError("the 'node' readout needs agent_id")
+            if not isinstance(agent_id, torch.Tensor) or not agent_id.is_cuda:
+                raise GnnError("agent_id must be a CUDA (HIP) tensor; there is no CPU fallback")
+            if agent_id.numel() != B:
+                raise GnnError("agent_id must be [B] or [B, 1], got %s" % (tuple(agent_id.shape),))
+            aid = agent_id.reshape(B)
+            if aid.dtype != torch.int64:
+                aid = aid.long()   # GNNBase.forward: agent_id.long()
+            aid = aid.contiguous()
+        sh = torch.cuda.current_stream(self.device).cuda_stream
+        out = self._out.get((B, sh))
+        if out is None:
+            if len(self._out) >= 8:
+                self._out.clear()
+            out = self._out[(B, sh)] = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=self.device)
+        rc = self.lib.lsm_gnn_forward(self._struct, C.c_void_p(self.weights.data_ptr()),
+                                      C.c_void_p(node_obs.data_ptr()), C.c_void_p(adj.data_ptr()),
+                                      C.c_void_p(masks.data_ptr()) if masks is not None else None, B, E, N,
+                                      C.c_void_p(aid.data_ptr()) if aid is not None else None,
+                                      C.c_void_p(out.data_ptr()), C.c_void_p(self.bad.data_ptr()), C.c_void_p(sh))
+        if rc != 0:
+            raise GnnError(self.lib.lsm_gnn_last_error().decode())
+        if check and int(self.bad.item()):
+            self.bad.zero_()
+            raise GnnError("an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the "
+                           "encoder")
+        return out
+
+    def forward(self, node_obs, adj, agent_id=None, check: bool = False):
+        """node_obs [B, E, F], adj [B, E, E] (the reference layout), agent_id [B, 1] or [B]."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        adj = self._tensor(adj, "adj", torch.float32, (B, E, E))
+        return self._run(node_obs, adj, None, B, E, 1, agent_id, check)
+
+    def forward_compact(self, node_obs, table, masks, num_agents: int, agent_id=None, check: bool = False):
+        """The compact layout: table [n, E, E], masks [n, N, W] (or [n * N, W]) int64 disconnect words,
+        node_obs [n * N, E, F]; graph b = env * N + ego."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        N = int(num_agents)
+        if N < 1 or B % N:
+            raise GnnError("node_obs holds %d graphs, not a multiple of num_agents = %d" % (B, N))
+        table = self._tensor(table, "table", torch.float32, (B // N, E, E))
+        if not isinstance(masks, torch.Tensor) or masks.numel() != B * ((E + 63) // 64):
+            raise GnnError("masks must hold [n * N, ceil(E / 64)] words")
+        masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", torch.int64, (B, (E + 63) // 64))
+        return self._run(node_obs, table, masks, B, E, N, agent_id, check)
+
+    __call__ = forward
