@@ -35,6 +35,8 @@ UNITS = {
     "lsm_mb_edges.hip": ["../../include/lsm_minibatch_edges.h"],
     # the fused graph-encoder forward (include/lsm_gnn.h, likewise outside build_id())
     "lsm_gnn.hip": ["../../include/lsm_gnn.h"],
+    # the fused actor / critic heads (include/lsm_policy.h, likewise outside build_id())
+    "lsm_policy.hip": ["../../include/lsm_policy.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
-``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h`` and ``include/lsm_gnn.h``
-(``liblsm_rollout.so``).
+``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h`` and
+``include/lsm_policy.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -60,6 +60,9 @@ LSM_MB_INDICES, LSM_MB_CHUNKS = 0, 1
 # Every symbol include/lsm_gnn.h declares (checked by tests/test_gnn_capi.py).
 EXPORTED_GNN = ("lsm_gnn_weights_floats", "lsm_gnn_forward", "lsm_host_gnn_forward", "lsm_gnn_last_error")
 LSM_GNN_NODE, LSM_GNN_GLOBAL_MEAN, LSM_GNN_GLOBAL_MAX, LSM_GNN_GLOBAL_ADD = 0, 1, 2, 3
+# Every symbol include/lsm_policy.h declares (checked by tests/test_policy_capi.py).
+EXPORTED_POLICY = ("lsm_head_weights_floats", "lsm_head_forward", "lsm_host_head_forward", "lsm_policy_last_error")
+LSM_HEAD_ACTOR, LSM_HEAD_CRITIC = 0, 1
 
 
 class LsmConfig(C.Structure):
@@ -131,6 +134,19 @@ class LsmGnnConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("F", "num_embeddings", "embedding_size", "embed_hidden", "embed_layer_N",
                                          "embed_relu", "layer_norm", "C", "H", "concat", "layer_N", "relu", "aggr",
                                          "ego_only")]
+
+
+class LsmHeadConfig(C.Structure):
+    """lsm_head_config (include/lsm_policy.h), passed by value."""
+    _fields_ = [(n, C.c_int32) for n in ("in0", "in1", "hidden", "layer_N", "relu", "feature_norm", "recurrent_N",
+                                         "kind", "num_actions")]
+
+
+class LsmHeadIo(C.Structure):
+    """lsm_head_io (include/lsm_policy.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("x0", "x1", "rnn_states", "masks", "u", "available_actions", "actions_i32",
+                                          "actions_f32", "log_probs", "logits", "values", "features", "rnn_out",
+                                          "bad")]
 
 
 class LsmError(RuntimeError):
@@ -214,6 +230,11 @@ def load_library(path: str = LIB_PATH):
         "lsm_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P, P]),
         "lsm_host_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P]),
         "lsm_gnn_last_error": (C.c_char_p, []),
+        # include/lsm_policy.h
+        "lsm_head_weights_floats": (SZ, [LsmHeadConfig]),
+        "lsm_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64, P]),
+        "lsm_host_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64]),
+        "lsm_policy_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

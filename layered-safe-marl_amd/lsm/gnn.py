@@ -257,4 +257,15 @@ class GraphEncoder:
         masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", torch.int64, (B, (E + 63) // 64))
         return self._run(node_obs, table, masks, B, E, N, agent_id, check)
 
+    def forward_step(self, node_obs, adj, adj_mask, num_agents: int, agent_id=None, check: bool = False):
+        """One step's graphs as a GpuGraphVecEnv or a DeviceGraphBuffer row holds them, in either adjacency
+        layout: node_obs [n, N, E, F]; adj [n, N, E, E] with adj_mask None (the reference layout), or the
+        table [n, E, E] with adj_mask [n, N, W] (the compact layout). Returns [n * N, out_dim]."""
+        E, F = int(node_obs.shape[-2]), int(node_obs.shape[-1])
+        node = node_obs.reshape(-1, E, F)
+        aid = None if agent_id is None else agent_id.reshape(-1)
+        if adj_mask is None:
+            return self.forward(node, adj.reshape(-1, E, E), aid, check=check)
+        return self.forward_compact(node, adj, adj_mask, num_agents, aid, check=check)
+
     __call__ = forward

@@ -1,0 +1,346 @@
+"""The rest of ``GR_Actor.forward`` / ``GR_Critic.forward`` after the graph encoder
+(``onpolicy/algorithms/graph_actor_critic.py:162-172, 406-418``) as one kernel launch per network
+(``csrc/lsm_policy.hip`` through ``include/lsm_policy.h``): the virtual ``cat([obs, nbd_features])``,
+``MLPBase``, the GRU ``RNNLayer``, ``ACTLayer``'s ``Categorical`` (sample or mode, log-probability) and the
+critic's ``v_out``.
+
+``PolicyHead.forward`` runs one head on device tensors; ``DevicePolicy.get_actions`` chains the two encoders
+(``lsm.gnn.GraphEncoder``) and the two heads on what the step left on the device and returns what
+``GR_MAPPOPolicy.get_actions`` returns, plus int32 ``[n, N]`` actions for ``step_async``: no host
+synchronisation and, with a replay buffer, no torch op besides the draw of the uniforms. Inference only
+(``collect``, evaluation): no backward pass, no ``evaluate_actions``, Discrete action spaces only, and no CPU
+fallback, as elsewhere in the project.
+
+Sampling is ``Categorical.sample`` as a distribution -- the inverse CDF of ``torch.rand`` uniforms -- not
+torch's generator stream: the same seed does not reproduce ``torch.multinomial``'s actions.
+
+Weights travel as one packed float32 blob per head (layout: ``include/lsm_policy.h``).
+``pack_head_weights`` builds it from a ``GR_Actor`` / ``GR_Critic`` state dict, checking every shape against
+the config; ``PolicyHead.load`` refreshes the device copy after an optimiser step.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import capi
+
+KINDS = {"actor": capi.LSM_HEAD_ACTOR, "critic": capi.LSM_HEAD_CRITIC}
+
+
+class PolicyError(RuntimeError):
+    pass
+
+
+def _torch():
+    import torch
+    return torch
+
+
+@dataclass(frozen=True)
+class HeadConfig:
+    """One head's shape: the fields of ``lsm_head_config``. kind: 'actor' or 'critic'; in0 / in1: the
+    widths of the two input blocks (obs or cent_obs, the encoder's output); recurrent_N = 0: no RNN. The
+    defaults are the reference's (onpolicy/config.py)."""
+    kind: str
+    in0: int
+    in1: int
+    hidden: int = 64
+    layer_N: int = 1
+    relu: bool = True
+    feature_norm: bool = True
+    recurrent_N: int = 1
+    num_actions: Optional[int] = None
+
+    @classmethod
+    def from_args(cls, all_args, kind: str, in0: int, in1: int, num_actions: Optional[int] = None) -> "HeadConfig":
+        """From the reference's argument names (recurrent_N counts only with use_recurrent_policy or
+        use_naive_recurrent_policy)."""
+        rnn = bool(all_args.use_recurrent_policy) or bool(all_args.use_naive_recurrent_policy)
+        return cls(kind=kind, in0=int(in0), in1=int(in1), hidden=int(all_args.hidden_size),
+                   layer_N=int(all_args.layer_N), relu=bool(all_args.use_ReLU),
+                   feature_norm=bool(all_args.use_feature_normalization),
+                   recurrent_N=int(all_args.recurrent_N) if rnn else 0,
+                   num_actions=None if num_actions is None else int(num_actions))
+
+    @property
+    def out_rows(self) -> int:
+        """Rows of the output Linear: num_actions (actor) or 1 (critic)."""
+        return int(self.num_actions) if self.kind == "actor" else 1
+
+    def struct(self) -> capi.LsmHeadConfig:
+        if self.kind not in KINDS:
+            raise ValueError("kind must be 'actor' or 'critic', got %r" % (self.kind,))
+        if self.kind == "actor" and self.num_actions is None:
+            raise ValueError("an actor head needs num_actions")
+        return capi.LsmHeadConfig(in0=self.in0, in1=self.in1, hidden=self.hidden, layer_N=self.layer_N,
+                                  relu=int(self.relu), feature_norm=int(self.feature_norm),
+                                  recurrent_N=self.recurrent_N, kind=KINDS[self.kind],
+                                  num_actions=int(self.num_actions or 0))
+
+
+def head_weight_entries(cfg: HeadConfig):
+    """[(state-dict name without prefix, shape)] in the blob's order (include/lsm_policy.h)."""
+    n, Hd = cfg.in0 + cfg.in1, cfg.hidden
+    out = [("base.feature_norm.weight", (n,)), ("base.feature_norm.bias", (n,)),
+           ("base.mlp.fc1.0.weight", (Hd, n)), ("base.mlp.fc1.0.bias", (Hd,)),
+           ("base.mlp.fc1.2.weight", (Hd,)), ("base.mlp.fc1.2.bias", (Hd,))]
+    for i in range(cfg.layer_N):
+        out += [("base.mlp.fc2.%d.0.weight" % i, (Hd, Hd)), ("base.mlp.fc2.%d.0.bias" % i, (Hd,)),
+                ("base.mlp.fc2.%d.2.weight" % i, (Hd,)), ("base.mlp.fc2.%d.2.bias" % i, (Hd,))]
+    for k in range(cfg.recurrent_N):
+        out += [("rnn.rnn.weight_ih_l%d" % k, (3 * Hd, Hd)), ("rnn.rnn.weight_hh_l%d" % k, (3 * Hd, Hd)),
+                ("rnn.rnn.bias_ih_l%d" % k, (3 * Hd,)), ("rnn.rnn.bias_hh_l%d" % k, (3 * Hd,))]
+    if cfg.recurrent_N > 0:
+        out += [("rnn.norm.weight", (Hd,)), ("rnn.norm.bias", (Hd,))]
+    last = "act.action_out.linear" if cfg.kind == "actor" else "v_out"
+    out += [(last + ".weight", (cfg.out_rows, Hd)), (last + ".bias", (cfg.out_rows,))]
+    return out
+
+
+def head_weights_floats(cfg: HeadConfig) -> int:
+    """lsm_head_weights_floats(cfg); raises for a config the library refuses."""
+    lib = capi.load_library()
+    n = int(lib.lsm_head_weights_floats(cfg.struct()))
+    if n == 0:
+        raise PolicyError(lib.lsm_policy_last_error().decode())
+    return n
+
+
+def pack_head_weights(state_dict, cfg: HeadConfig, prefix: str = "") -> np.ndarray:
+    """The packed float32 blob of a GR_Actor / GR_Critic state dict (tensors or arrays). Every entry's
+    shape is checked against cfg; a missing or mis-shaped one is refused by name. Without feature
+    normalisation the state dict has no base.feature_norm entries and the blob's unread gamma / beta are
+    1 / 0. Entries the forward pass does not use (base.mlp.fc_h.*, gnn_base.*, PopArt's statistics) are
+    ignored."""
+    parts = []
+    for name, shape in head_weight_entries(cfg):
+        key = prefix + name
+        if key not in state_dict:
+            if name.startswith("base.feature_norm.") and not cfg.feature_norm:
+                parts.append(np.full(shape, 1.0 if name.endswith("weight") else 0.0, np.float32))
+                continue
+            raise PolicyError("pack_head_weights: %s is missing from the state dict" % key)
+        v = state_dict[key]
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        if tuple(a.shape) != shape:
+            raise PolicyError("pack_head_weights: %s has shape %s, the config needs %s" % (key, tuple(a.shape), shape))
+        parts.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
+    blob = np.concatenate(parts)
+    if blob.size != head_weights_floats(cfg):
+        raise PolicyError("pack_head_weights: %d floats packed, the library expects %d"
+                          % (blob.size, head_weights_floats(cfg)))
+    return blob
+
+
+def unpack_head_weights(blob, cfg: HeadConfig, prefix: str = ""):
+    """The inverse of pack_head_weights: {name: float32 array} (feature_norm entries only with it on)."""
+    blob = np.asarray(blob, dtype=np.float32).reshape(-1)
+    if blob.size != head_weights_floats(cfg):
+        raise PolicyError("unpack_head_weights: blob of %d floats, the config needs %d"
+                          % (blob.size, head_weights_floats(cfg)))
+    out, o = {}, 0
+    for name, shape in head_weight_entries(cfg):
+        n = int(np.prod(shape))
+        if cfg.feature_norm or not name.startswith("base.feature_norm."):
+            out[prefix + name] = blob[o:o + n].reshape(shape).copy()
+        o += n
+    return out
+
+
+class PolicyHead:
+    """One head on the GPU for one config and one weight blob.
+
+    forward() returns a dict of output tensors preallocated per (M, stream), valid until the next call
+    with that M on that stream. check=True reads the call's bad-input word (one synchronisation) and
+    raises when a uniform was not in [0, 1); by default the word is not read."""
+
+    def __init__(self, cfg: HeadConfig, weights, device):
+        torch = _torch()
+        self.cfg = cfg
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise PolicyError("PolicyHead needs a CUDA (HIP) device; there is no CPU fallback")
+        self.lib = capi.load_library()
+        self._struct = cfg.struct()
+        self._n = head_weights_floats(cfg)
+        self.weights = torch.empty(self._n, dtype=torch.float32, device=self.device)
+        self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self._out = {}
+        self._set(weights)
+
+    def _set(self, blob):
+        torch = _torch()
+        if isinstance(blob, torch.Tensor):
+            src = blob.detach().reshape(-1).to(torch.float32)
+        else:
+            src = torch.from_numpy(np.ascontiguousarray(blob, dtype=np.float32).reshape(-1))
+        if src.numel() != self._n:
+            raise PolicyError("weight blob of %d floats, the config needs %d" % (src.numel(), self._n))
+        self.weights.copy_(src, non_blocking=True)   # the one device copy, on the current stream
+
+    def load(self, state_dict, prefix: str = ""):
+        """Refresh the blob from a GR_Actor / GR_Critic state dict (after each optimiser step)."""
+        self._set(pack_head_weights(state_dict, self.cfg, prefix))
+
+    def _tensor(self, t, name, numel):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise PolicyError("%s must be a CUDA (HIP) tensor; there is no CPU fallback" % name)
+        if t.device != self.device:
+            raise PolicyError("%s is on %s, the head on %s" % (name, t.device, self.device))
+        if t.dtype != torch.float32 or t.numel() != numel:
+            raise PolicyError("%s must hold %d float32 values, got %s %s" % (name, numel, t.dtype, tuple(t.shape)))
+        return t if t.is_contiguous() else t.contiguous()
+
+    def _outputs(self, M, sh):
+        torch = _torch()
+        out = self._out.get((M, sh))
+        if out is None:
+            if len(self._out) >= 8:
+                self._out.clear()
+            cfg, dev, f32 = self.cfg, self.device, torch.float32
+            out = {"features": torch.empty((M, cfg.hidden), dtype=f32, device=dev)}
+            if cfg.recurrent_N:
+                out["rnn_states"] = torch.empty((M, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
+            if cfg.kind == "actor":
+                out["actions_env"] = torch.empty((M,), dtype=torch.int32, device=dev)
+                out["actions"] = torch.empty((M, 1), dtype=f32, device=dev)
+                out["action_log_probs"] = torch.empty((M, 1), dtype=f32, device=dev)
+            else:
+                out["values"] = torch.empty((M, 1), dtype=f32, device=dev)
+            self._out[(M, sh)] = out
+        return out
+
+    def forward(self, x0, x1, rnn_states=None, masks=None, u=None, available_actions=None, check: bool = False):
+        """x0 [M, in0] (None when in0 == 0), x1 [M, in1], rnn_states [M, recurrent_N, hidden], masks [M, 1]
+        or [M], u [M] uniforms in [0, 1) (None: the mode), available_actions [M, num_actions] float32.
+        Actor: {actions_env int32 [M], actions [M, 1], action_log_probs [M, 1], features, rnn_states};
+        critic: {values [M, 1], features, rnn_states} (rnn_states only with an RNN)."""
+        cfg = self.cfg
+        torch = _torch()
+        if not isinstance(x1, torch.Tensor) or x1.dim() < 1:
+            raise PolicyError("x1 must be a CUDA (HIP) tensor [M, in1]; there is no CPU fallback")
+        if cfg.in1 < 1:
+            raise PolicyError("PolicyHead.forward takes the row count from x1: the config needs in1 >= 1")
+        M = x1.numel() // cfg.in1
+        x1 = self._tensor(x1, "x1", M * cfg.in1)
+        if cfg.in0:
+            if x0 is None:
+                raise PolicyError("the head was built with in0 = %d: x0 is needed" % cfg.in0)
+            x0 = self._tensor(x0, "x0", M * cfg.in0)
+        else:
+            x0 = None
+        if cfg.recurrent_N:
+            if rnn_states is None or masks is None:
+                raise PolicyError("a recurrent head needs rnn_states and masks")
+            rnn_states = self._tensor(rnn_states, "rnn_states", M * cfg.recurrent_N * cfg.hidden)
+            masks = self._tensor(masks, "masks", M)
+        else:
+            rnn_states = masks = None
+        actor = cfg.kind == "actor"
+        if actor and u is not None:
+            u = self._tensor(u, "u", M)
+        if actor and available_actions is not None:
+            available_actions = self._tensor(available_actions, "available_actions", M * cfg.num_actions)
+        sh = torch.cuda.current_stream(self.device).cuda_stream
+        out = self._outputs(M, sh)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        io = capi.LsmHeadIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks),
+                            u=ptr(u) if actor else None, available_actions=ptr(available_actions) if actor else None,
+                            actions_i32=ptr(out.get("actions_env")), actions_f32=ptr(out.get("actions")),
+                            log_probs=ptr(out.get("action_log_probs")), logits=None, values=ptr(out.get("values")),
+                            features=ptr(out["features"]), rnn_out=ptr(out.get("rnn_states")),
+                            bad=self.bad.data_ptr())
+        rc = self.lib.lsm_head_forward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), M,
+                                       C.c_void_p(sh))
+        if rc != 0:
+            raise PolicyError(self.lib.lsm_policy_last_error().decode())
+        if check and int(self.bad.item()):
+            self.bad.zero_()
+            raise PolicyError("a uniform outside [0, 1) reached the sampler")
+        return out
+
+    __call__ = forward
+
+
+class DevicePolicy:
+    """GR_MAPPOPolicy.get_actions on the device: the actor's and the critic's encoder and head, four
+    launches on what the step left behind.
+
+    actor_encoder / critic_encoder: lsm.gnn.GraphEncoder; actor_head / critic_head: PolicyHead. The
+    critic's 'node' aggregation (critic_graph_aggr == 'node': all agents' rows concatenated,
+    gnn_out_dim * num_agents wide) is not what the encoder produces and is refused; the default 'global' works."""
+
+    def __init__(self, actor_encoder, actor_head, critic_encoder, critic_head):
+        if actor_head.cfg.kind != "actor" or critic_head.cfg.kind != "critic":
+            raise PolicyError("DevicePolicy takes (actor_encoder, actor_head, critic_encoder, critic_head)")
+        if critic_encoder.cfg.aggr == "node":
+            raise PolicyError("the critic's 'node' aggregation concatenates every agent's encoder row "
+                              "(gnn_out_dim * num_agents); the encoder does not produce that: use "
+                              "critic_graph_aggr = 'global'")
+        for enc, head, what in ((actor_encoder, actor_head, "actor"), (critic_encoder, critic_head, "critic")):
+            if head.cfg.in1 != enc.cfg.out_dim:
+                raise PolicyError("the %s head's in1 = %d, its encoder's out_dim = %d"
+                                  % (what, head.cfg.in1, enc.cfg.out_dim))
+        if actor_head.cfg.recurrent_N != critic_head.cfg.recurrent_N or actor_head.cfg.hidden != critic_head.cfg.hidden:
+            raise PolicyError("the two heads differ in recurrent_N or hidden")
+        self.actor_encoder, self.actor_head = actor_encoder, actor_head
+        self.critic_encoder, self.critic_head = critic_encoder, critic_head
+        self.last_actor = self.last_critic = None   # the heads' own output dicts of the last call (features too)
+
+    def get_actions(self, env, rnn_states, rnn_states_critic, masks, deterministic: bool = False, generator=None,
+                    available_actions=None, buffer=None):
+        """One collect step's policy outputs for env (a GpuGraphVecEnv with return_numpy=False). The
+        inputs are read where the last step or reset wrote them: the env's own tensors, or, with
+        buffer (a DeviceGraphBuffer bound to env, whose rings take the step's outputs instead), row
+        buffer.step of the buffer. rnn_states / rnn_states_critic [M, recurrent_N, hidden] and masks [M, 1]
+        (or their [n, N, ...] buffer rows) are ignored without an RNN.
+
+        Returns device tensors: values [M, 1], actions [M, 1] float32, action_log_probs [M, 1], rnn_states
+        and rnn_states_critic [M, recurrent_N, hidden] (the inputs themselves without an RNN), actions_env
+        int32 [n, N]. They are valid until the next call."""
+        torch = _torch()
+        if env.return_numpy:
+            raise PolicyError("DevicePolicy needs an env built with return_numpy=False")
+        n, N, OBS = env.num_envs, env.N, env.OBS
+        M = n * N
+        if buffer is None:
+            obs, node, adj, adj_mask, share = env.t_obs, env.t_node, env.t_adj, env.t_adj_mask, None
+        else:
+            if buffer.env is not env:
+                raise PolicyError("buffer belongs to another env")
+            t = buffer.step
+            obs, node, adj, share = buffer.obs[t], buffer.node_obs[t], buffer.adj[t], buffer.share_obs[t]
+            adj_mask = None if buffer.adj_mask is None else buffer.adj_mask[t]
+        ah, ch = self.actor_head.cfg, self.critic_head.cfg
+        if ah.in0 != OBS:
+            raise PolicyError("the actor head's in0 = %d, the env's obs are %d wide" % (ah.in0, OBS))
+        cent = None
+        if ch.in0:
+            if share is not None and share.shape[-1] == ch.in0:
+                cent = share
+            elif ch.in0 == OBS:
+                cent = obs
+            elif ch.in0 == N * OBS:
+                # without a buffer there is no share_obs row: every agent's row is the env's obs, concatenated
+                cent = obs.reshape(n, 1, N * OBS).expand(n, N, N * OBS).contiguous()
+            else:
+                raise PolicyError("the critic head's in0 = %d is neither the obs width %d nor the shared %d"
+                                  % (ch.in0, OBS, N * OBS))
+        u = None if deterministic else torch.rand(M, generator=generator, device=env.device, dtype=torch.float32)
+        a_feat = self.actor_encoder.forward_step(node, adj, adj_mask, N, env.agent_id)
+        a = self.actor_head.forward(obs, a_feat, rnn_states, masks, u=u, available_actions=available_actions)
+        c_feat = self.critic_encoder.forward_step(node, adj, adj_mask, N, env.agent_id)
+        c = self.critic_head.forward(cent, c_feat, rnn_states_critic, masks)
+        self.last_actor, self.last_critic = a, c
+        return {"values": c["values"], "actions": a["actions"], "action_log_probs": a["action_log_probs"],
+                "rnn_states": a.get("rnn_states", rnn_states),
+                "rnn_states_critic": c.get("rnn_states", rnn_states_critic),
+                "actions_env": a["actions_env"].view(n, N)}

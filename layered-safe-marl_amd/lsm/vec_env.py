@@ -396,11 +396,7 @@ class GpuGraphVecEnv(ShareVecEnv):
         """The graph encoder's output [n * N, out_dim] (lsm.gnn.GraphEncoder, GNNBase.forward) for the
         current node features, per-ego adjacencies and agent ids, read where the step left them in
         either adjacency layout: the companion of edge_list(), with no edge list built."""
-        node = self.t_node.view(-1, self.E, self.F)
-        aid = self.agent_id.view(-1)
-        if self.t_adj_mask is None:
-            return encoder.forward(node, self.t_adj.view(-1, self.E, self.E), aid, check=check)
-        return encoder.forward_compact(node, self.t_adj, self.t_adj_mask, self.N, aid, check=check)
+        return encoder.forward_step(self.t_node, self.t_adj, self.t_adj_mask, self.N, self.agent_id, check=check)
 
     def set_agent_state(self, env_index: int, agent_state, reached=None):
         """Overwrite one env's agent states ([N][4]) and optionally reached_goal ([N])."""
