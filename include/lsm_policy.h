@@ -3,8 +3,8 @@
  * (onpolicy/algorithms/graph_actor_critic.py:162-172, 406-418) run after GNNBase.forward -- the
  * cat([obs, nbd_features]), MLPBase, the GRU RNNLayer, ACTLayer's Categorical (sample or mode, with the
  * log-probability) and the critic's v_out -- for M rows in one launch. Inference only (GMPERunner.collect
- * and evaluation, under torch.no_grad()): no backward pass, no evaluate_actions, no entropy; Discrete
- * action spaces only.
+ * and evaluation, under torch.no_grad()): no backward pass; Discrete action spaces only. The sequence form
+ * (evaluate_actions on a minibatch: the stored action's log-probability, the entropy) is lsm_evaluate.h.
  *
  * What is computed per row m (all arithmetic float32; Hd = hidden, in = in0 + in1). The row's input is
  * x = [x0[m][0 .. in0), x1[m][0 .. in1)]; the concatenation is never materialised in memory. in0 == 0 with a
@@ -14,7 +14,7 @@
  * 2. MLPLayer: y = LayerNorm(Hd)(act(fc1 x)), then layer_N times y = LayerNorm(Hd)(act(fc2[i] y)), act
  *    ReLU or Tanh. These LayerNorms do not depend on feature_norm. The fc2[i] are separate weights; the
  *    state dict's base.mlp.fc_h.*, the template they were cloned from, is not used by forward and not packed.
- * 3. RNNLayer, when recurrent_N > 0 (the one-step branch; the T x N sequence branch is training only):
+ * 3. RNNLayer, when recurrent_N > 0 (the one-step branch; the T x N sequence branch is lsm_evaluate.h):
  *    h_l = rnn_states[m][l] * masks[m] (a product, as in the reference: a non-finite state under a zero mask
  *    stays non-finite). For l = 0 .. recurrent_N - 1, x_0 = y, x_l = h'_(l-1), torch's GRU cell, gates r, z, n:
  *      r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)      z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)

@@ -1,0 +1,310 @@
+// lsm_head_tile.h -- the per-row pieces of the actor / critic heads that the one-step kernel
+// (lsm_policy.hip, include/lsm_policy.h) and the sequence kernel (lsm_evaluate.hip, include/lsm_evaluate.h)
+// both run: the config's checks and the weight blob's offsets, dot4 / linear / layer_norm, the input
+// staging, MLPBase, one GRU layer's cells and the masked softmax's first two walks. Every function is ONE
+// __host__ __device__ text: the host entry points run it with a tile of one row and one "wave".
+//
+// Work split and LDS layout are described in lsm_policy.hip; what a piece expects of the barriers around
+// it stands at the piece.
+#ifndef LSM_HEAD_TILE_H
+#define LSM_HEAD_TILE_H
+
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/lsm_policy.h"
+
+// the text of lsm_policy_last_error() (thread-local, lsm_policy.hip): "<prefix><msg>"
+__attribute__((visibility("hidden"))) void lsm_policy_set_error(const char* prefix, const char* msg);
+
+namespace lsm_head_tile {
+
+#define LSM_HD __host__ __device__ __forceinline__
+#if defined(__HIP_DEVICE_COMPILE__)
+#define LSM_SYNC() __syncthreads()
+#else
+#define LSM_SYNC() ((void)0)
+#endif
+
+constexpr int BLOCK = 256;
+constexpr int TILE = 64;            // rows per workgroup, lane = row
+constexpr int WAVES = BLOCK / TILE;
+constexpr int MAX_IN = 256, MAX_HIDDEN = 128, MAX_LAYERS = 4, MAX_RNN = 2, MAX_ACTIONS = 64;
+constexpr int MAX_DEVICES = 64;
+constexpr int WORKGROUP_LDS_BYTES = 163840;   // 160 KB: what one workgroup can have
+
+// the head's shape and the offsets of its weights in the packed blob
+struct Shape {
+  int32_t in0, in1, in, Hd, L, relu, fnorm, RN, kind, A;
+  int32_t SX, SA;          // padded LDS row strides: the input row, an activation row
+  int32_t o_fn, o_fc[MAX_LAYERS + 1], o_gru[MAX_RNN], o_rn, o_out;
+};
+
+LSM_HD float fma_(float a, float b, float c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_fmaf(a, b, c);
+#else
+  return a * b + c;
+#endif
+}
+
+LSM_HD float rsq_(float v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return rsqrtf(v);
+#else
+  return 1.0f / sqrtf(v);
+#endif
+}
+
+LSM_HD float sigmoid_(float v) { return 1.0f / (1.0f + expf(-v)); }
+
+// acc[jj] += <w[jj * ld + 0 .. n), row[0 .. n)> for jj < nj <= 4 (the other accumulators follow row 0 and
+// are dropped by the caller); row is a 16-byte aligned LDS row. Each product sum runs as four partial sums
+// over the inputs i mod 4 (inputs ascending, the first one starting from acc[jj]), added as (p0 + p1) +
+// (p2 + p3), then the n mod 4 last inputs in turn: a fixed order with a quarter of the sequential sum's
+// rounding growth, and sixteen independent FMA chains per 16-byte read
+LSM_HD void dot4(const float* __restrict__ w, int ld, int nj, const float* row, int n, float (&acc)[4]) {
+  const float* __restrict__ w0 = w;
+  const float* __restrict__ w1 = w + (nj > 1 ? ld : 0);
+  const float* __restrict__ w2 = w + (nj > 2 ? 2 * ld : 0);
+  const float* __restrict__ w3 = w + (nj > 3 ? 3 * ld : 0);
+  float p0[4] = {acc[0], 0.0f, 0.0f, 0.0f}, p1[4] = {acc[1], 0.0f, 0.0f, 0.0f};
+  float p2[4] = {acc[2], 0.0f, 0.0f, 0.0f}, p3[4] = {acc[3], 0.0f, 0.0f, 0.0f};
+  int i = 0;
+  for (; i + 4 <= n; i += 4) {
+    const float4 h = *reinterpret_cast<const float4*>(row + i);
+    p0[0] = fma_(w0[i], h.x, p0[0]);
+    p1[0] = fma_(w1[i], h.x, p1[0]);
+    p2[0] = fma_(w2[i], h.x, p2[0]);
+    p3[0] = fma_(w3[i], h.x, p3[0]);
+    p0[1] = fma_(w0[i + 1], h.y, p0[1]);
+    p1[1] = fma_(w1[i + 1], h.y, p1[1]);
+    p2[1] = fma_(w2[i + 1], h.y, p2[1]);
+    p3[1] = fma_(w3[i + 1], h.y, p3[1]);
+    p0[2] = fma_(w0[i + 2], h.z, p0[2]);
+    p1[2] = fma_(w1[i + 2], h.z, p1[2]);
+    p2[2] = fma_(w2[i + 2], h.z, p2[2]);
+    p3[2] = fma_(w3[i + 2], h.z, p3[2]);
+    p0[3] = fma_(w0[i + 3], h.w, p0[3]);
+    p1[3] = fma_(w1[i + 3], h.w, p1[3]);
+    p2[3] = fma_(w2[i + 3], h.w, p2[3]);
+    p3[3] = fma_(w3[i + 3], h.w, p3[3]);
+  }
+  acc[0] = (p0[0] + p0[1]) + (p0[2] + p0[3]);
+  acc[1] = (p1[0] + p1[1]) + (p1[2] + p1[3]);
+  acc[2] = (p2[0] + p2[1]) + (p2[2] + p2[3]);
+  acc[3] = (p3[0] + p3[1]) + (p3[2] + p3[3]);
+  for (; i < n; ++i) {
+    const float h = row[i];
+    acc[0] = fma_(w0[i], h, acc[0]);
+    acc[1] = fma_(w1[i], h, acc[1]);
+    acc[2] = fma_(w2[i], h, acc[2]);
+    acc[3] = fma_(w3[i], h, acc[3]);
+  }
+}
+
+// the four accumulators of output block j0 start from the bias
+LSM_HD void bias4(const float* __restrict__ b, int nj, float (&acc)[4]) {
+#pragma unroll
+  for (int jj = 0; jj < 4; ++jj) acc[jj] = b[jj < nj ? jj : 0];
+}
+
+// dst[0 .. nout) = act(W src + b) for this wave's column blocks. act: 0 none, 1 ReLU (NaN stays NaN), 2 Tanh
+LSM_HD void linear(const float* __restrict__ W, const float* __restrict__ b, int nout, int nin, const float* src,
+                   float* dst, int wv, int nw, int act) {
+  for (int j0 = 4 * wv; j0 < nout; j0 += 4 * nw) {
+    const int nj = nout - j0 < 4 ? nout - j0 : 4;
+    float acc[4];
+    bias4(b + j0, nj, acc);
+    dot4(W + (int64_t)j0 * nin, nin, nj, src, nin, acc);
+    if (act == 1) {
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) acc[jj] = acc[jj] < 0.0f ? 0.0f : acc[jj];
+    } else if (act == 2) {
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) acc[jj] = tanhf(acc[jj]);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj)
+      if (jj < nj) dst[j0 + jj] = acc[jj];
+  }
+}
+
+// the sum of f(row[i]) over i < n as four partial sums over i mod 4, (p0 + p1) + (p2 + p3), then the
+// n mod 4 last ones in turn; f(v) = v - sub, squared when sq
+LSM_HD float row_sum(const float* row, int n, float sub, bool sq) {
+  float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  int i = 0;
+  for (; i + 4 <= n; i += 4) {
+    const float4 h = *reinterpret_cast<const float4*>(row + i);
+    const float d[4] = {h.x - sub, h.y - sub, h.z - sub, h.w - sub};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) p[k] = sq ? fma_(d[k], d[k], p[k]) : p[k] + d[k];
+  }
+  float s = (p[0] + p[1]) + (p[2] + p[3]);
+  for (; i < n; ++i) {
+    const float d = row[i] - sub;
+    s = sq ? fma_(d, d, s) : s + d;
+  }
+  return s;
+}
+
+// nn.LayerNorm(n) of src's row into dst's row: the statistics over the whole row in every wave (the same
+// order in each, so the waves hold the same bits), the wave's own column blocks written. src == dst needs
+// the barrier between the two halves.
+LSM_HD void layer_norm(const float* src, float* dst, int n, const float* __restrict__ gamma,
+                       const float* __restrict__ beta, int wv, int nw) {
+  const float mean = row_sum(src, n, 0.0f, false) / (float)n;
+  const float rs = rsq_(row_sum(src, n, mean, true) / (float)n + 1e-5f);
+  if (src == dst) LSM_SYNC();
+  for (int j0 = 4 * wv; j0 < n; j0 += 4 * nw)
+    for (int j = j0; j < n && j < j0 + 4; ++j) dst[j] = fma_((src[j] - mean) * rs, gamma[j], beta[j]);
+}
+
+// the virtual cat([x0, x1]) of rows row0 .. row0 + rows - 1: one LDS row per tile row, read coalesced. The
+// caller's barrier follows.
+LSM_HD void load_inputs(const Shape& n, const float* x0, const float* x1, int64_t row0, int rows, float* X, int tid,
+                        int nt) {
+  const int SX = n.SX;
+  for (int k = tid; k < rows * n.in0; k += nt) {
+    const int r = k / n.in0, c = k - r * n.in0;
+    X[r * SX + c] = x0[row0 * n.in0 + k];
+  }
+  for (int k = tid; k < rows * n.in1; k += nt) {
+    const int r = k / n.in1, c = k - r * n.in1;
+    X[r * SX + n.in0 + c] = x1[row0 * n.in1 + k];
+  }
+}
+
+// MLPBase on the lane's staged input row: the feature norm, then fc1 and fc2[i], each Linear, activation,
+// LayerNorm. xrow is overwritten by the feature norm; the result is in cur (nxt is scratch); the last
+// barrier has been passed on return.
+LSM_HD void mlp(const Shape& n, const float* __restrict__ w, float* xrow, float* cur, float* nxt, int wv, int nw) {
+  const int in = n.in, Hd = n.Hd;
+  if (n.fnorm) {
+    layer_norm(xrow, xrow, in, w + n.o_fn, w + n.o_fn + in, wv, nw);
+    LSM_SYNC();
+  }
+  for (int k = 0; k <= n.L; ++k) {
+    const int din = k == 0 ? in : Hd;
+    const float* W = w + n.o_fc[k];
+    const float* b = W + Hd * din;
+    linear(W, b, Hd, din, k == 0 ? xrow : cur, nxt, wv, nw, n.relu ? 1 : 2);
+    LSM_SYNC();
+    layer_norm(nxt, cur, Hd, b + Hd, b + 2 * Hd, wv, nw);
+    LSM_SYNC();
+  }
+}
+
+// GRU layer l of the lane's row: o[j] = h'_j for this wave's column blocks, from the layer's input x and
+// its state h (both whole LDS rows; h already holds state * mask). No barrier inside: the caller's follows.
+LSM_HD void gru_layer(const Shape& n, const float* __restrict__ w, int l, const float* x, const float* h, float* o,
+                      int wv, int nw) {
+  const int Hd = n.Hd;
+  const float* Wih = w + n.o_gru[l];
+  const float* Whh = Wih + 3 * Hd * Hd;
+  const float* bih = Whh + 3 * Hd * Hd;
+  const float* bhh = bih + 3 * Hd;
+  for (int j0 = 4 * wv; j0 < Hd; j0 += 4 * nw) {
+    const int nj = Hd - j0 < 4 ? Hd - j0 : 4;
+    float ir[4], iz[4], ig[4], hr[4], hz[4], hg[4];
+    bias4(bih + j0, nj, ir);
+    bias4(bih + Hd + j0, nj, iz);
+    bias4(bih + 2 * Hd + j0, nj, ig);
+    bias4(bhh + j0, nj, hr);
+    bias4(bhh + Hd + j0, nj, hz);
+    bias4(bhh + 2 * Hd + j0, nj, hg);
+    dot4(Wih + j0 * Hd, Hd, nj, x, Hd, ir);
+    dot4(Wih + (Hd + j0) * Hd, Hd, nj, x, Hd, iz);
+    dot4(Wih + (2 * Hd + j0) * Hd, Hd, nj, x, Hd, ig);
+    dot4(Whh + j0 * Hd, Hd, nj, h, Hd, hr);
+    dot4(Whh + (Hd + j0) * Hd, Hd, nj, h, Hd, hz);
+    dot4(Whh + (2 * Hd + j0) * Hd, Hd, nj, h, Hd, hg);
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      if (jj >= nj) continue;
+      const float r = sigmoid_(ir[jj] + hr[jj]);
+      const float z = sigmoid_(iz[jj] + hz[jj]);
+      const float g = tanhf(fma_(r, hg[jj], ig[jj]));
+      const float hp = fma_(z, h[j0 + jj], (1.0f - z) * g);
+      o[j0 + jj] = hp;
+    }
+  }
+}
+
+// The first two walks over a row's A logits, a ascending, in one lane: the availability mask (-FLT_MAX where
+// avail[a] == 0; avail NULL: none), written back to lg and, when given, to logits; mx, the first a
+// attaining it, and s = sum of exp(lg[a] - mx).
+LSM_HD void masked_softmax(float* lg, int A, const float* avail, float* logits, float& mx, int& first, float& s) {
+  mx = 0.0f;
+  first = 0;
+  for (int a = 0; a < A; ++a) {
+    float l = lg[a];
+    if (avail && avail[a] == 0.0f) l = -FLT_MAX;
+    lg[a] = l;
+    if (logits) logits[a] = l;
+    if (a == 0 || l > mx) mx = l, first = a;
+  }
+  s = 0.0f;
+  for (int a = 0; a < A; ++a) s += expf(lg[a] - mx);
+}
+
+// ---- host side: the config's checks ----------------------------------------------------------------------
+
+constexpr int pad(int w) { return ((w + 3) & ~3) + 4; }
+
+inline bool in_range(int v, int lo, int hi) { return v >= lo && v <= hi; }
+
+inline bool overlap(const void* a, const void* b, size_t bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + bytes && y < x + bytes;
+}
+
+// the config's checks and the blob's offsets; returns the blob's length in floats, 0 with a text
+// ("<prefix>...") on refusal
+inline size_t layout(const lsm_head_config& c, Shape* n, const char* prefix) {
+  auto fail = [prefix](const char* msg) { return lsm_policy_set_error(prefix, msg), (size_t)0; };
+  if (c.in0 < 0 || c.in1 < 0) return fail("in0 and in1 must be >= 0");
+  if (c.in0 > MAX_IN || c.in1 > MAX_IN || !in_range(c.in0 + c.in1, 1, MAX_IN))
+    return fail("in0 + in1 must be in [1, 256]");
+  if (!in_range(c.hidden, 1, MAX_HIDDEN)) return fail("hidden must be in [1, 128]");
+  if (!in_range(c.layer_N, 0, MAX_LAYERS)) return fail("layer_N must be in [0, 4]");
+  if (!in_range(c.recurrent_N, 0, MAX_RNN)) return fail("recurrent_N must be in [0, 2]");
+  if (c.kind != LSM_HEAD_ACTOR && c.kind != LSM_HEAD_CRITIC) return fail("unknown kind");
+  if (c.kind == LSM_HEAD_ACTOR && !in_range(c.num_actions, 1, MAX_ACTIONS))
+    return fail("num_actions must be in [1, 64]");
+  n->in0 = c.in0;
+  n->in1 = c.in1;
+  n->in = c.in0 + c.in1;
+  n->Hd = c.hidden;
+  n->L = c.layer_N;
+  n->relu = c.relu != 0;
+  n->fnorm = c.feature_norm != 0;
+  n->RN = c.recurrent_N;
+  n->kind = c.kind;
+  n->A = c.kind == LSM_HEAD_ACTOR ? c.num_actions : 1;
+  const int Hd = n->Hd;
+  int o = 0;
+  n->o_fn = o, o += 2 * n->in;
+  for (int k = 0; k <= MAX_LAYERS; ++k) {
+    n->o_fc[k] = o;
+    if (k <= n->L) o += Hd * (k == 0 ? n->in : Hd) + 3 * Hd;
+  }
+  for (int l = 0; l < MAX_RNN; ++l) {
+    n->o_gru[l] = o;
+    if (l < n->RN) o += 6 * Hd * Hd + 6 * Hd;
+  }
+  n->o_rn = o;
+  if (n->RN > 0) o += 2 * Hd;
+  n->o_out = o, o += n->A * Hd + n->A;
+  n->SX = pad(n->in > Hd ? n->in : Hd);
+  n->SA = pad(Hd > n->A ? Hd : n->A);
+  return (size_t)o;
+}
+
+}  // namespace lsm_head_tile
+#endif

@@ -28,7 +28,8 @@
 // multiple of 64 banks (lane r's row starts 4 (r mod 16) banks on for width 64).
 //
 // tile_forward is ONE __host__ __device__ text; lsm_host_head_forward runs it with a tile of one row and
-// one "wave".
+// one "wave". The per-row pieces (dot4, linear, layer_norm, the GRU cells, the softmax walks) and the
+// config's checks live in lsm_head_tile.h, which the sequence kernel (lsm_evaluate.hip) runs too.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -39,151 +40,17 @@
 #include <vector>
 
 #include "../../include/lsm_policy.h"
+#include "lsm_head_tile.h"   // the per-row pieces, shared with the sequence kernel (lsm_evaluate.hip)
 
 namespace {
 
-#define LSM_HD __host__ __device__ __forceinline__
-#if defined(__HIP_DEVICE_COMPILE__)
-#define LSM_SYNC() __syncthreads()
-#else
-#define LSM_SYNC() ((void)0)
-#endif
+using namespace lsm_head_tile;
 
-constexpr int BLOCK = 256;
-constexpr int TILE = 64;            // rows per workgroup, lane = row
-constexpr int WAVES = BLOCK / TILE;
-constexpr int MAX_IN = 256, MAX_HIDDEN = 128, MAX_LAYERS = 4, MAX_RNN = 2, MAX_ACTIONS = 64;
-constexpr int MAX_DEVICES = 64;
-
-struct Head {
+struct Head : Shape {
   const float* w;
   lsm_head_io io;
   int64_t M;
-  int32_t in0, in1, in, Hd, L, relu, fnorm, RN, kind, A;
-  int32_t SX, SA;          // padded LDS row strides: the input row, an activation row
-  int32_t o_fn, o_fc[MAX_LAYERS + 1], o_gru[MAX_RNN], o_rn, o_out;
 };
-
-LSM_HD float fma_(float a, float b, float c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_fmaf(a, b, c);
-#else
-  return a * b + c;
-#endif
-}
-
-LSM_HD float rsq_(float v) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return rsqrtf(v);
-#else
-  return 1.0f / sqrtf(v);
-#endif
-}
-
-LSM_HD float sigmoid_(float v) { return 1.0f / (1.0f + expf(-v)); }
-
-// acc[jj] += <w[jj * ld + 0 .. n), row[0 .. n)> for jj < nj <= 4 (the other accumulators follow row 0 and
-// are dropped by the caller); row is a 16-byte aligned LDS row. Each product sum runs as four partial sums
-// over the inputs i mod 4 (inputs ascending, the first one starting from acc[jj]), added as (p0 + p1) +
-// (p2 + p3), then the n mod 4 last inputs in turn: a fixed order with a quarter of the sequential sum's
-// rounding growth, and sixteen independent FMA chains per 16-byte read
-LSM_HD void dot4(const float* __restrict__ w, int ld, int nj, const float* row, int n, float (&acc)[4]) {
-  const float* __restrict__ w0 = w;
-  const float* __restrict__ w1 = w + (nj > 1 ? ld : 0);
-  const float* __restrict__ w2 = w + (nj > 2 ? 2 * ld : 0);
-  const float* __restrict__ w3 = w + (nj > 3 ? 3 * ld : 0);
-  float p0[4] = {acc[0], 0.0f, 0.0f, 0.0f}, p1[4] = {acc[1], 0.0f, 0.0f, 0.0f};
-  float p2[4] = {acc[2], 0.0f, 0.0f, 0.0f}, p3[4] = {acc[3], 0.0f, 0.0f, 0.0f};
-  int i = 0;
-  for (; i + 4 <= n; i += 4) {
-    const float4 h = *reinterpret_cast<const float4*>(row + i);
-    p0[0] = fma_(w0[i], h.x, p0[0]);
-    p1[0] = fma_(w1[i], h.x, p1[0]);
-    p2[0] = fma_(w2[i], h.x, p2[0]);
-    p3[0] = fma_(w3[i], h.x, p3[0]);
-    p0[1] = fma_(w0[i + 1], h.y, p0[1]);
-    p1[1] = fma_(w1[i + 1], h.y, p1[1]);
-    p2[1] = fma_(w2[i + 1], h.y, p2[1]);
-    p3[1] = fma_(w3[i + 1], h.y, p3[1]);
-    p0[2] = fma_(w0[i + 2], h.z, p0[2]);
-    p1[2] = fma_(w1[i + 2], h.z, p1[2]);
-    p2[2] = fma_(w2[i + 2], h.z, p2[2]);
-    p3[2] = fma_(w3[i + 2], h.z, p3[2]);
-    p0[3] = fma_(w0[i + 3], h.w, p0[3]);
-    p1[3] = fma_(w1[i + 3], h.w, p1[3]);
-    p2[3] = fma_(w2[i + 3], h.w, p2[3]);
-    p3[3] = fma_(w3[i + 3], h.w, p3[3]);
-  }
-  acc[0] = (p0[0] + p0[1]) + (p0[2] + p0[3]);
-  acc[1] = (p1[0] + p1[1]) + (p1[2] + p1[3]);
-  acc[2] = (p2[0] + p2[1]) + (p2[2] + p2[3]);
-  acc[3] = (p3[0] + p3[1]) + (p3[2] + p3[3]);
-  for (; i < n; ++i) {
-    const float h = row[i];
-    acc[0] = fma_(w0[i], h, acc[0]);
-    acc[1] = fma_(w1[i], h, acc[1]);
-    acc[2] = fma_(w2[i], h, acc[2]);
-    acc[3] = fma_(w3[i], h, acc[3]);
-  }
-}
-
-// the four accumulators of output block j0 start from the bias
-LSM_HD void bias4(const float* __restrict__ b, int nj, float (&acc)[4]) {
-#pragma unroll
-  for (int jj = 0; jj < 4; ++jj) acc[jj] = b[jj < nj ? jj : 0];
-}
-
-// dst[0 .. nout) = act(W src + b) for this wave's column blocks. act: 0 none, 1 ReLU (NaN stays NaN), 2 Tanh
-LSM_HD void linear(const float* __restrict__ W, const float* __restrict__ b, int nout, int nin, const float* src,
-                   float* dst, int wv, int nw, int act) {
-  for (int j0 = 4 * wv; j0 < nout; j0 += 4 * nw) {
-    const int nj = nout - j0 < 4 ? nout - j0 : 4;
-    float acc[4];
-    bias4(b + j0, nj, acc);
-    dot4(W + (int64_t)j0 * nin, nin, nj, src, nin, acc);
-    if (act == 1) {
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[jj] = acc[jj] < 0.0f ? 0.0f : acc[jj];
-    } else if (act == 2) {
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) acc[jj] = tanhf(acc[jj]);
-    }
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj)
-      if (jj < nj) dst[j0 + jj] = acc[jj];
-  }
-}
-
-// the sum of f(row[i]) over i < n as four partial sums over i mod 4, (p0 + p1) + (p2 + p3), then the
-// n mod 4 last ones in turn; f(v) = v - sub, squared when sq
-LSM_HD float row_sum(const float* row, int n, float sub, bool sq) {
-  float p[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  int i = 0;
-  for (; i + 4 <= n; i += 4) {
-    const float4 h = *reinterpret_cast<const float4*>(row + i);
-    const float d[4] = {h.x - sub, h.y - sub, h.z - sub, h.w - sub};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) p[k] = sq ? fma_(d[k], d[k], p[k]) : p[k] + d[k];
-  }
-  float s = (p[0] + p[1]) + (p[2] + p[3]);
-  for (; i < n; ++i) {
-    const float d = row[i] - sub;
-    s = sq ? fma_(d, d, s) : s + d;
-  }
-  return s;
-}
-
-// nn.LayerNorm(n) of src's row into dst's row: the statistics over the whole row in every wave (the same
-// order in each, so the waves hold the same bits), the wave's own column blocks written. src == dst needs
-// the barrier between the two halves.
-LSM_HD void layer_norm(const float* src, float* dst, int n, const float* __restrict__ gamma,
-                       const float* __restrict__ beta, int wv, int nw) {
-  const float mean = row_sum(src, n, 0.0f, false) / (float)n;
-  const float rs = rsq_(row_sum(src, n, mean, true) / (float)n + 1e-5f);
-  if (src == dst) LSM_SYNC();
-  for (int j0 = 4 * wv; j0 < n; j0 += 4 * nw)
-    for (int j = j0; j < n && j < j0 + 4; ++j) dst[j] = fma_((src[j] - mean) * rs, gamma[j], beta[j]);
-}
 
 // One tile: rows row0 .. row0 + rows - 1, lane = row (lane >= rows: an idle lane that keeps the barriers
 // uniform and writes nothing), wave wv of nw; R = the tile's capacity in rows (64 on the device, 1 on the host).
@@ -192,7 +59,7 @@ LSM_HD void layer_norm(const float* src, float* dst, int n, const float* __restr
 LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row0, int rows, int lane, int wv, int nw,
                          int R, float* lds) {
   const int tid = wv * R + lane, nt = nw * R;
-  const int in = n.in, Hd = n.Hd, SX = n.SX, SA = n.SA, RN = n.RN;
+  const int Hd = n.Hd, SX = n.SX, SA = n.SA, RN = n.RN;
   float* X = lds;
   float* cur = X + R * SX;
   float* nxt = cur + R * SA;
@@ -200,31 +67,10 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
   const int64_t m = row0 + lane;
   float* xrow = X + lane * SX;
 
-  // ---- the virtual cat([x0, x1]): one LDS row per tile row, read coalesced --------------------------
-  for (int k = tid; k < rows * n.in0; k += nt) {
-    const int r = k / n.in0, c = k - r * n.in0;
-    X[r * SX + c] = n.io.x0[row0 * n.in0 + k];
-  }
-  for (int k = tid; k < rows * n.in1; k += nt) {
-    const int r = k / n.in1, c = k - r * n.in1;
-    X[r * SX + n.in0 + c] = n.io.x1[row0 * n.in1 + k];
-  }
+  // ---- the virtual cat([x0, x1]), the feature norm and MLPLayer --------------------------------------------
+  load_inputs(n, n.io.x0, n.io.x1, row0, rows, X, tid, nt);
   LSM_SYNC();
-  if (n.fnorm) {
-    layer_norm(xrow, xrow, in, w + n.o_fn, w + n.o_fn + in, wv, nw);
-    LSM_SYNC();
-  }
-
-  // ---- MLPLayer: fc1, fc2[i]; each Linear, activation, LayerNorm ---------------------------------------
-  for (int k = 0; k <= n.L; ++k) {
-    const int din = k == 0 ? in : Hd;
-    const float* W = w + n.o_fc[k];
-    const float* b = W + Hd * din;
-    linear(W, b, Hd, din, k == 0 ? xrow : cur + lane * SA, nxt + lane * SA, wv, nw, n.relu ? 1 : 2);
-    LSM_SYNC();
-    layer_norm(nxt + lane * SA, cur + lane * SA, Hd, b + Hd, b + 2 * Hd, wv, nw);
-    LSM_SYNC();
-  }
+  mlp(n, w, xrow, cur + lane * SA, nxt + lane * SA, wv, nw);
 
   // ---- RNNLayer: recurrent_N GRU cells on h = state * mask, then its norm --------------------------------
   for (int l = 0; l < RN; ++l) {
@@ -233,37 +79,7 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
       X[r * SX + c] = n.io.rnn_states[((row0 + r) * RN + l) * Hd + c] * n.io.masks[row0 + r];
     }
     LSM_SYNC();
-    const float* Wih = w + n.o_gru[l];
-    const float* Whh = Wih + 3 * Hd * Hd;
-    const float* bih = Whh + 3 * Hd * Hd;
-    const float* bhh = bih + 3 * Hd;
-    const float* x = cur + lane * SA;
-    float* o = nxt + lane * SA;
-    for (int j0 = 4 * wv; j0 < Hd; j0 += 4 * nw) {
-      const int nj = Hd - j0 < 4 ? Hd - j0 : 4;
-      float ir[4], iz[4], ig[4], hr[4], hz[4], hg[4];
-      bias4(bih + j0, nj, ir);
-      bias4(bih + Hd + j0, nj, iz);
-      bias4(bih + 2 * Hd + j0, nj, ig);
-      bias4(bhh + j0, nj, hr);
-      bias4(bhh + Hd + j0, nj, hz);
-      bias4(bhh + 2 * Hd + j0, nj, hg);
-      dot4(Wih + j0 * Hd, Hd, nj, x, Hd, ir);
-      dot4(Wih + (Hd + j0) * Hd, Hd, nj, x, Hd, iz);
-      dot4(Wih + (2 * Hd + j0) * Hd, Hd, nj, x, Hd, ig);
-      dot4(Whh + j0 * Hd, Hd, nj, xrow, Hd, hr);
-      dot4(Whh + (Hd + j0) * Hd, Hd, nj, xrow, Hd, hz);
-      dot4(Whh + (2 * Hd + j0) * Hd, Hd, nj, xrow, Hd, hg);
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        if (jj >= nj) continue;
-        const float r = sigmoid_(ir[jj] + hr[jj]);
-        const float z = sigmoid_(iz[jj] + hz[jj]);
-        const float g = tanhf(fma_(r, hg[jj], ig[jj]));
-        const float hp = fma_(z, xrow[j0 + jj], (1.0f - z) * g);
-        o[j0 + jj] = hp;
-      }
-    }
+    gru_layer(n, w, l, cur + lane * SA, xrow, nxt + lane * SA, wv, nw);
     LSM_SYNC();
     float* t = cur;
     cur = nxt;
@@ -304,17 +120,10 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
   linear(Wo, Wo + A * Hd, A, Hd, feat, lg, wv, nw, 0);
   LSM_SYNC();
   if (wv != 0 || !active) return;
-  float mx = 0.0f;
-  int first = 0;
-  for (int a = 0; a < A; ++a) {
-    float l = lg[a];
-    if (n.io.available_actions && n.io.available_actions[m * A + a] == 0.0f) l = -FLT_MAX;
-    lg[a] = l;
-    if (n.io.logits) n.io.logits[m * A + a] = l;
-    if (a == 0 || l > mx) mx = l, first = a;
-  }
-  float s = 0.0f;
-  for (int a = 0; a < A; ++a) s += expf(lg[a] - mx);
+  float mx, s;
+  int first;
+  masked_softmax(lg, A, n.io.available_actions ? n.io.available_actions + m * A : nullptr,
+                 n.io.logits ? n.io.logits + m * A : nullptr, mx, first, s);
   int pick = first;
   if (n.io.u) {
     float u = n.io.u[m];
@@ -352,66 +161,17 @@ __global__ __launch_bounds__(BLOCK) void head_kernel(Head n, const float* __rest
 thread_local char g_err[256];
 
 int fail(const char* msg) {
-  snprintf(g_err, sizeof g_err, "head: %s", msg);
+  lsm_policy_set_error("head: ", msg);
   return 1;
 }
 
-constexpr int pad(int w) { return ((w + 3) & ~3) + 4; }
-
 // the largest tile the limits allow (in = 256, hidden = 128): 134144 bytes, within one workgroup's 160 KB
 constexpr int MAX_TILE_BYTES = TILE * (pad(MAX_IN) + 2 * pad(MAX_HIDDEN)) * (int)sizeof(float);
-static_assert(MAX_TILE_BYTES <= 163840, "the worst-case tile must fit one workgroup's LDS");
-
-bool in_range(int v, int lo, int hi) { return v >= lo && v <= hi; }
-
-// the config's checks and the blob's offsets; returns the blob's length in floats, 0 with a text on refusal
-size_t layout(const lsm_head_config& c, Head* n) {
-  if (c.in0 < 0 || c.in1 < 0) return fail("in0 and in1 must be >= 0"), 0;
-  if (c.in0 > MAX_IN || c.in1 > MAX_IN || !in_range(c.in0 + c.in1, 1, MAX_IN))
-    return fail("in0 + in1 must be in [1, 256]"), 0;
-  if (!in_range(c.hidden, 1, MAX_HIDDEN)) return fail("hidden must be in [1, 128]"), 0;
-  if (!in_range(c.layer_N, 0, MAX_LAYERS)) return fail("layer_N must be in [0, 4]"), 0;
-  if (!in_range(c.recurrent_N, 0, MAX_RNN)) return fail("recurrent_N must be in [0, 2]"), 0;
-  if (c.kind != LSM_HEAD_ACTOR && c.kind != LSM_HEAD_CRITIC) return fail("unknown kind"), 0;
-  if (c.kind == LSM_HEAD_ACTOR && !in_range(c.num_actions, 1, MAX_ACTIONS))
-    return fail("num_actions must be in [1, 64]"), 0;
-  n->in0 = c.in0;
-  n->in1 = c.in1;
-  n->in = c.in0 + c.in1;
-  n->Hd = c.hidden;
-  n->L = c.layer_N;
-  n->relu = c.relu != 0;
-  n->fnorm = c.feature_norm != 0;
-  n->RN = c.recurrent_N;
-  n->kind = c.kind;
-  n->A = c.kind == LSM_HEAD_ACTOR ? c.num_actions : 1;
-  const int Hd = n->Hd;
-  int o = 0;
-  n->o_fn = o, o += 2 * n->in;
-  for (int k = 0; k <= MAX_LAYERS; ++k) {
-    n->o_fc[k] = o;
-    if (k <= n->L) o += Hd * (k == 0 ? n->in : Hd) + 3 * Hd;
-  }
-  for (int l = 0; l < MAX_RNN; ++l) {
-    n->o_gru[l] = o;
-    if (l < n->RN) o += 6 * Hd * Hd + 6 * Hd;
-  }
-  n->o_rn = o;
-  if (n->RN > 0) o += 2 * Hd;
-  n->o_out = o, o += n->A * Hd + n->A;
-  n->SX = pad(n->in > Hd ? n->in : Hd);
-  n->SA = pad(Hd > n->A ? Hd : n->A);
-  return (size_t)o;
-}
-
-bool overlap(const void* a, const void* b, size_t bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
-}
+static_assert(MAX_TILE_BYTES <= WORKGROUP_LDS_BYTES, "the worst-case tile must fit one workgroup's LDS");
 
 // every check of one call, shared by the device and the host entry point; fills n; 0 when fine
 int make_head(const lsm_head_config& c, const float* weights, const lsm_head_io* io, int64_t M, Head* n) {
-  if (layout(c, n) == 0) return 1;
+  if (layout(c, n, "head: ") == 0) return 1;
   if (!weights) return fail("weights is null");
   if (!io) return fail("io is null");
   if (M < 0) return fail("M < 0");
@@ -449,13 +209,17 @@ int make_head(const lsm_head_config& c, const float* weights, const lsm_head_io*
 
 }  // namespace
 
+void lsm_policy_set_error(const char* prefix, const char* msg) {
+  snprintf(g_err, sizeof g_err, "%s%s", prefix, msg);
+}
+
 extern "C" {
 
 const char* lsm_policy_last_error(void) { return g_err; }
 
 size_t lsm_head_weights_floats(lsm_head_config cfg) {
-  Head n;
-  return layout(cfg, &n);
+  Shape n;
+  return layout(cfg, &n, "head: ");
 }
 
 int lsm_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_io* io, int64_t M, void* hip_stream) {

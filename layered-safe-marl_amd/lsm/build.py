@@ -36,7 +36,10 @@ UNITS = {
     # the fused graph-encoder forward (include/lsm_gnn.h, likewise outside build_id())
     "lsm_gnn.hip": ["../../include/lsm_gnn.h"],
     # the fused actor / critic heads (include/lsm_policy.h, likewise outside build_id())
-    "lsm_policy.hip": ["../../include/lsm_policy.h"],
+    "lsm_policy.hip": ["../../include/lsm_policy.h", "lsm_head_tile.h"],
+    # the heads' sequence form (include/lsm_evaluate.h, likewise outside build_id()); lsm_head_tile.h holds
+    # the per-row pieces the two units share
+    "lsm_evaluate.hip": ["../../include/lsm_evaluate.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -63,6 +63,8 @@ LSM_GNN_NODE, LSM_GNN_GLOBAL_MEAN, LSM_GNN_GLOBAL_MAX, LSM_GNN_GLOBAL_ADD = 0, 1
 # Every symbol include/lsm_policy.h declares (checked by tests/test_policy_capi.py).
 EXPORTED_POLICY = ("lsm_head_weights_floats", "lsm_head_forward", "lsm_host_head_forward", "lsm_policy_last_error")
 LSM_HEAD_ACTOR, LSM_HEAD_CRITIC = 0, 1
+# Every symbol include/lsm_evaluate.h declares (checked by tests/test_evaluate_capi.py).
+EXPORTED_EVALUATE = ("lsm_head_evaluate_scratch_bytes", "lsm_head_evaluate", "lsm_host_head_evaluate")
 
 
 class LsmConfig(C.Structure):
@@ -147,6 +149,13 @@ class LsmHeadIo(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("x0", "x1", "rnn_states", "masks", "u", "available_actions", "actions_i32",
                                           "actions_f32", "log_probs", "logits", "values", "features", "rnn_out",
                                           "bad")]
+
+
+class LsmEvalIo(C.Structure):
+    """lsm_eval_io (include/lsm_evaluate.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("x0", "x1", "rnn_states", "masks", "actions", "available_actions",
+                                          "active_masks", "log_probs", "entropy", "dist_entropy", "logits", "values",
+                                          "features", "rnn_out", "scratch", "bad")]
 
 
 class LsmError(RuntimeError):
@@ -235,6 +244,10 @@ def load_library(path: str = LIB_PATH):
         "lsm_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64, P]),
         "lsm_host_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64]),
         "lsm_policy_last_error": (C.c_char_p, []),
+        # include/lsm_evaluate.h
+        "lsm_head_evaluate_scratch_bytes": (SZ, [I64, I32]),
+        "lsm_head_evaluate": (I32, [LsmHeadConfig, P, C.POINTER(LsmEvalIo), I64, I32, P]),
+        "lsm_host_head_evaluate": (I32, [LsmHeadConfig, P, C.POINTER(LsmEvalIo), I64, I32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -7,9 +7,13 @@ critic's ``v_out``.
 ``PolicyHead.forward`` runs one head on device tensors; ``DevicePolicy.get_actions`` chains the two encoders
 (``lsm.gnn.GraphEncoder``) and the two heads on what the step left on the device and returns what
 ``GR_MAPPOPolicy.get_actions`` returns, plus int32 ``[n, N]`` actions for ``step_async``: no host
-synchronisation and, with a replay buffer, no torch op besides the draw of the uniforms. Inference only
-(``collect``, evaluation): no backward pass, no ``evaluate_actions``, Discrete action spaces only, and no CPU
-fallback, as elsewhere in the project.
+synchronisation and, with a replay buffer, no torch op besides the draw of the uniforms.
+``DevicePolicy.get_values`` and ``DevicePolicy.act`` are its two halves (``GMPERunner.compute``, the
+evaluation loop). ``PolicyHead.evaluate`` and ``DevicePolicy.evaluate_actions`` are the sequence form
+(``csrc/lsm_evaluate.hip`` through ``include/lsm_evaluate.h``): on a minibatch of ``recurrent_generator`` or
+``feed_forward_generator`` the GRU state is carried through each chunk's steps, and the log-probability of
+the stored action, the entropy and the values come back. Forward passes only: no backward pass, Discrete
+action spaces only, and no CPU fallback, as elsewhere in the project.
 
 Sampling is ``Categorical.sample`` as a distribution -- the inverse CDF of ``torch.rand`` uniforms -- not
 torch's generator stream: the same seed does not reproduce ``torch.multinomial``'s actions.
@@ -170,6 +174,7 @@ class PolicyHead:
         self.weights = torch.empty(self._n, dtype=torch.float32, device=self.device)
         self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._out = {}
+        self._eval_out = {}
         self._set(weights)
 
     def _set(self, blob):
@@ -269,10 +274,101 @@ class PolicyHead:
 
     __call__ = forward
 
+    def _eval_outputs(self, Cn, T, sh):
+        torch = _torch()
+        out = self._eval_out.get((Cn, T, sh))
+        if out is None:
+            if len(self._eval_out) >= 8:
+                self._eval_out.clear()
+            cfg, dev, f32, R = self.cfg, self.device, torch.float32, Cn * T
+            out = {"features": torch.empty((R, cfg.hidden), dtype=f32, device=dev)}
+            if cfg.recurrent_N:
+                out["rnn_states"] = torch.empty((Cn, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
+            if cfg.kind == "actor":
+                out["action_log_probs"] = torch.empty((R, 1), dtype=f32, device=dev)
+                out["entropy"] = torch.empty((R,), dtype=f32, device=dev)
+                out["dist_entropy"] = torch.empty((), dtype=f32, device=dev)
+                nbytes = int(self.lib.lsm_head_evaluate_scratch_bytes(Cn, T))
+                out["_scratch"] = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+            else:
+                out["values"] = torch.empty((R, 1), dtype=f32, device=dev)
+            self._eval_out[(Cn, T, sh)] = out
+        return out
+
+    def evaluate(self, x0, x1, rnn_states, masks, T, actions=None, available_actions=None, active_masks=None,
+                 check: bool = False):
+        """The sequence form (include/lsm_evaluate.h) on a time-major minibatch of C chunks of T steps, as
+        recurrent_generator yields it: x0 [T*C, in0] (None when in0 == 0), x1 [T*C, in1], rnn_states
+        [C, recurrent_N, hidden] (each chunk's state at its first step), masks [T*C, 1] or [T*C], actions
+        [T*C, 1] float32 (actor), available_actions [T*C, num_actions], active_masks [T*C, 1] (the weights of
+        dist_entropy; None: the mean). T=None: feed-forward rows (T = 1). Returns preallocated device
+        tensors, cached per (C, T, stream) and valid until the next call with them:
+        actor {action_log_probs [T*C, 1], entropy [T*C], dist_entropy (0-dim), features, rnn_states};
+        critic {values [T*C, 1], features, rnn_states} (rnn_states [C, recurrent_N, hidden]: the state
+        after the last step, only with an RNN). check=True reads the bad-input word (one synchronisation)
+        and raises when a stored action was not an integer in [0, num_actions)."""
+        cfg = self.cfg
+        torch = _torch()
+        if not isinstance(x1, torch.Tensor) or x1.dim() < 1:
+            raise PolicyError("x1 must be a CUDA (HIP) tensor [T*C, in1]; there is no CPU fallback")
+        if cfg.in1 < 1:
+            raise PolicyError("PolicyHead.evaluate takes the row count from x1: the config needs in1 >= 1")
+        T = 1 if T is None else int(T)
+        R = x1.numel() // cfg.in1
+        if T < 1 or R % T:
+            raise PolicyError("%d rows are not chunks of T = %d steps" % (R, T))
+        Cn = R // T
+        x1 = self._tensor(x1, "x1", R * cfg.in1)
+        if cfg.in0:
+            if x0 is None:
+                raise PolicyError("the head was built with in0 = %d: x0 is needed" % cfg.in0)
+            x0 = self._tensor(x0, "x0", R * cfg.in0)
+        else:
+            x0 = None
+        if cfg.recurrent_N:
+            if rnn_states is None or masks is None:
+                raise PolicyError("a recurrent head needs rnn_states and masks")
+            rnn_states = self._tensor(rnn_states, "rnn_states", Cn * cfg.recurrent_N * cfg.hidden)
+            masks = self._tensor(masks, "masks", R)
+        else:
+            rnn_states = masks = None
+        actor = cfg.kind == "actor"
+        if actor:
+            if actions is None:
+                raise PolicyError("the actor evaluates stored actions: actions is needed")
+            actions = self._tensor(actions, "actions", R)
+            if available_actions is not None:
+                available_actions = self._tensor(available_actions, "available_actions", R * cfg.num_actions)
+            if active_masks is not None:
+                active_masks = self._tensor(active_masks, "active_masks", R)
+        else:
+            actions = available_actions = active_masks = None
+        sh = torch.cuda.current_stream(self.device).cuda_stream
+        out = self._eval_outputs(Cn, T, sh)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        io = capi.LsmEvalIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks), actions=ptr(actions),
+                            available_actions=ptr(available_actions), active_masks=ptr(active_masks),
+                            log_probs=ptr(out.get("action_log_probs")), entropy=ptr(out.get("entropy")),
+                            dist_entropy=ptr(out.get("dist_entropy")), logits=None, values=ptr(out.get("values")),
+                            features=ptr(out["features"]), rnn_out=ptr(out.get("rnn_states")),
+                            scratch=ptr(out.get("_scratch")), bad=self.bad.data_ptr())
+        rc = self.lib.lsm_head_evaluate(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), Cn, T,
+                                        C.c_void_p(sh))
+        if rc != 0:
+            raise PolicyError(self.lib.lsm_policy_last_error().decode())
+        if check and int(self.bad.item()):
+            self.bad.zero_()
+            raise PolicyError("a stored action that is not an integer in [0, num_actions) reached evaluate")
+        return out
+
 
 class DevicePolicy:
-    """GR_MAPPOPolicy.get_actions on the device: the actor's and the critic's encoder and head, four
-    launches on what the step left behind.
+    """GR_MAPPOPolicy's forward methods on the device. get_actions: the actor's and the critic's encoder and
+    head, four launches on what the step left behind; act and get_values: its actor and critic halves;
+    evaluate_actions: both encoders and the heads' sequence form on a minibatch of the buffer's generators.
 
     actor_encoder / critic_encoder: lsm.gnn.GraphEncoder; actor_head / critic_head: PolicyHead. The
     critic's 'node' aggregation (critic_graph_aggr == 'node': all agents' rows concatenated,
@@ -306,22 +402,55 @@ class DevicePolicy:
         Returns device tensors: values [M, 1], actions [M, 1] float32, action_log_probs [M, 1], rnn_states
         and rnn_states_critic [M, recurrent_N, hidden] (the inputs themselves without an RNN), actions_env
         int32 [n, N]. They are valid until the next call."""
-        torch = _torch()
+        src = self._step_inputs(env, buffer)
+        cent = self._cent_obs(env, src)
+        a = self._act(env, src, rnn_states, masks, deterministic, generator, available_actions)
+        c = self._values(env, src, cent, rnn_states_critic, masks)
+        return {"values": c["values"], "actions": a["actions"], "action_log_probs": a["action_log_probs"],
+                "rnn_states": a.get("rnn_states", rnn_states),
+                "rnn_states_critic": c.get("rnn_states", rnn_states_critic),
+                "actions_env": a["actions_env"].view(env.num_envs, env.N)}
+
+    def get_values(self, env, rnn_states_critic, masks, buffer=None, row=None):
+        """GR_MAPPOPolicy.get_values: the critic half of get_actions alone (the critic's encoder and head,
+        two launches), on the same inputs -- row buffer.step of buffer (or its row `row`), or the env's own
+        tensors. GMPERunner.compute calls it on the last row before compute_returns: after the T-th
+        insert_step buffer.step has wrapped to 0, so that call passes row=-1. Returns values [M, 1], valid
+        until the critic head's next call."""
+        src = self._step_inputs(env, buffer, row)
+        return self._values(env, src, self._cent_obs(env, src), rnn_states_critic, masks)["values"]
+
+    def act(self, env, rnn_states, masks, deterministic: bool = True, generator=None, available_actions=None,
+            buffer=None):
+        """GR_MAPPOPolicy.act: the actor half of get_actions alone (the actor's encoder and head, two
+        launches), deterministic by default as in the evaluation loop. Returns {actions [M, 1] float32,
+        actions_env int32 [n, N], rnn_states [M, recurrent_N, hidden] (the input itself without an RNN)}."""
+        src = self._step_inputs(env, buffer)
+        a = self._act(env, src, rnn_states, masks, deterministic, generator, available_actions)
+        return {"actions": a["actions"], "actions_env": a["actions_env"].view(env.num_envs, env.N),
+                "rnn_states": a.get("rnn_states", rnn_states)}
+
+    def _step_inputs(self, env, buffer, row=None):
+        """(obs, node_obs, adj, adj_mask, share_obs) where the last step or reset wrote them."""
         if env.return_numpy:
             raise PolicyError("DevicePolicy needs an env built with return_numpy=False")
-        n, N, OBS = env.num_envs, env.N, env.OBS
-        M = n * N
         if buffer is None:
             obs, node, adj, adj_mask, share = env.t_obs, env.t_node, env.t_adj, env.t_adj_mask, None
         else:
             if buffer.env is not env:
                 raise PolicyError("buffer belongs to another env")
-            t = buffer.step
+            t = buffer.step if row is None else int(row)
             obs, node, adj, share = buffer.obs[t], buffer.node_obs[t], buffer.adj[t], buffer.share_obs[t]
             adj_mask = None if buffer.adj_mask is None else buffer.adj_mask[t]
-        ah, ch = self.actor_head.cfg, self.critic_head.cfg
-        if ah.in0 != OBS:
-            raise PolicyError("the actor head's in0 = %d, the env's obs are %d wide" % (ah.in0, OBS))
+        if self.actor_head.cfg.in0 != env.OBS:
+            raise PolicyError("the actor head's in0 = %d, the env's obs are %d wide" % (self.actor_head.cfg.in0, env.OBS))
+        return obs, node, adj, adj_mask, share
+
+    def _cent_obs(self, env, src):
+        """The critic head's first input block, chosen by its width: share_obs, obs, or nothing."""
+        obs, share = src[0], src[4]
+        n, N, OBS = env.num_envs, env.N, env.OBS
+        ch = self.critic_head.cfg
         cent = None
         if ch.in0:
             if share is not None and share.shape[-1] == ch.in0:
@@ -334,13 +463,60 @@ class DevicePolicy:
             else:
                 raise PolicyError("the critic head's in0 = %d is neither the obs width %d nor the shared %d"
                                   % (ch.in0, OBS, N * OBS))
+        return cent
+
+    def _act(self, env, src, rnn_states, masks, deterministic, generator, available_actions):
+        torch = _torch()
+        obs, node, adj, adj_mask, _ = src
+        M = env.num_envs * env.N
         u = None if deterministic else torch.rand(M, generator=generator, device=env.device, dtype=torch.float32)
-        a_feat = self.actor_encoder.forward_step(node, adj, adj_mask, N, env.agent_id)
+        a_feat = self.actor_encoder.forward_step(node, adj, adj_mask, env.N, env.agent_id)
         a = self.actor_head.forward(obs, a_feat, rnn_states, masks, u=u, available_actions=available_actions)
-        c_feat = self.critic_encoder.forward_step(node, adj, adj_mask, N, env.agent_id)
+        self.last_actor = a
+        return a
+
+    def _values(self, env, src, cent, rnn_states_critic, masks):
+        _, node, adj, adj_mask, _ = src
+        c_feat = self.critic_encoder.forward_step(node, adj, adj_mask, env.N, env.agent_id)
         c = self.critic_head.forward(cent, c_feat, rnn_states_critic, masks)
+        self.last_critic = c
+        return c
+
+    def evaluate_actions(self, mb, data_chunk_length=None, check: bool = False):
+        """GR_MAPPOPolicy.evaluate_actions on one minibatch: a dict yielded by
+        DeviceGraphBuffer.recurrent_generator (data_chunk_length: the generator's) or by
+        feed_forward_generator (data_chunk_length None; the learner adds its own 'actions' rows, and
+        'available_actions' if it has them, gathered with the yielded indices). Both encoders run
+        GraphEncoder.forward(mb['node_obs'], mb['adj'], mb['agent_id']), both heads their sequence form
+        (PolicyHead.evaluate): six launches, no host synchronisation, no torch op besides views. The
+        critic's first input block is mb['share_obs'] or mb['obs'], whichever has its width.
+
+        Returns device tensors, valid until the next call: values [L*C, 1], action_log_probs [L*C, 1],
+        dist_entropy (0-dim; weighted by mb['active_masks'] when the batch has them) and entropy [L*C]."""
+        ah, ch = self.actor_head.cfg, self.critic_head.cfg
+        if mb.get("adj") is None:
+            raise PolicyError("the minibatch has no dense adj (edges=True): the encoder reads the [B, E, E] matrix")
+        obs = mb["obs"]
+        if obs.shape[-1] != ah.in0:
+            raise PolicyError("the actor head's in0 = %d, the minibatch's obs are %d wide" % (ah.in0, obs.shape[-1]))
+        cent = None
+        if ch.in0:
+            share = mb.get("share_obs")
+            if share is not None and share.shape[-1] == ch.in0:
+                cent = share
+            elif obs.shape[-1] == ch.in0:
+                cent = obs
+            else:
+                raise PolicyError("the critic head's in0 = %d is the width of neither share_obs nor obs" % ch.in0)
+        if mb.get("actions") is None:
+            raise PolicyError("the minibatch has no 'actions' rows to evaluate")
+        T = None if data_chunk_length is None else int(data_chunk_length)
+        a_feat = self.actor_encoder.forward(mb["node_obs"], mb["adj"], mb["agent_id"])
+        a = self.actor_head.evaluate(obs, a_feat, mb.get("rnn_states"), mb.get("masks"), T, actions=mb["actions"],
+                                     available_actions=mb.get("available_actions"),
+                                     active_masks=mb.get("active_masks"), check=check)
+        c_feat = self.critic_encoder.forward(mb["node_obs"], mb["adj"], mb["agent_id"])
+        c = self.critic_head.evaluate(cent, c_feat, mb.get("rnn_states_critic"), mb.get("masks"), T)
         self.last_actor, self.last_critic = a, c
-        return {"values": c["values"], "actions": a["actions"], "action_log_probs": a["action_log_probs"],
-                "rnn_states": a.get("rnn_states", rnn_states),
-                "rnn_states_critic": c.get("rnn_states", rnn_states_critic),
-                "actions_env": a["actions_env"].view(n, N)}
+        return {"values": c["values"], "action_log_probs": a["action_log_probs"], "dist_entropy": a["dist_entropy"],
+                "entropy": a["entropy"]}
