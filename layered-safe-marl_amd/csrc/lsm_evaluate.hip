@@ -45,14 +45,6 @@ struct Eval : Shape {
   int32_t SH;   // padded LDS row stride of a GRU state row
 };
 
-// the header's clamp of a stored action; flags what it had to change
-LSM_HD int clamp_action(float a, int A, bool& bad) {
-  bad = !(a >= 0.0f && a < (float)A && a == floorf(a));
-  if (!(a == a)) return 0;
-  const float c = a < 0.0f ? 0.0f : a > (float)(A - 1) ? (float)(A - 1) : a;
-  return (int)c;
-}
-
 // One tile: chunks b0 .. b0 + rows - 1, lane = chunk (lane >= rows: an idle lane that keeps the barriers
 // uniform and writes nothing), wave wv of nw; R = the tile's capacity in chunks (64 on the device, 1 on the
 // host). part[0 .. 2): the tile's dist_entropy sums (entropy * weight, weight), written when

@@ -253,6 +253,14 @@ LSM_HD void masked_softmax(float* lg, int A, const float* avail, float* logits, 
   for (int a = 0; a < A; ++a) s += expf(lg[a] - mx);
 }
 
+// include/lsm_evaluate.h's clamp of a stored action (lsm_evaluate.hip, lsm_loss.hip); flags what it had to change
+LSM_HD int clamp_action(float a, int A, bool& bad) {
+  bad = !(a >= 0.0f && a < (float)A && a == floorf(a));
+  if (!(a == a)) return 0;
+  const float c = a < 0.0f ? 0.0f : a > (float)(A - 1) ? (float)(A - 1) : a;
+  return (int)c;
+}
+
 // ---- host side: the config's checks ----------------------------------------------------------------------
 
 constexpr int pad(int w) { return ((w + 3) & ~3) + 4; }

@@ -40,6 +40,8 @@ UNITS = {
     # the heads' sequence form (include/lsm_evaluate.h, likewise outside build_id()); lsm_head_tile.h holds
     # the per-row pieces the two units share
     "lsm_evaluate.hip": ["../../include/lsm_evaluate.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
+    # the PPO loss and its gradient at the heads' outputs (include/lsm_loss.h, likewise outside build_id())
+    "lsm_loss.hip": ["../../include/lsm_loss.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
-``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h`` and
-``include/lsm_policy.h`` (``liblsm_rollout.so``).
+``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
+``include/lsm_policy.h``, ``include/lsm_evaluate.h`` and ``include/lsm_loss.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -65,6 +65,9 @@ EXPORTED_POLICY = ("lsm_head_weights_floats", "lsm_head_forward", "lsm_host_head
 LSM_HEAD_ACTOR, LSM_HEAD_CRITIC = 0, 1
 # Every symbol include/lsm_evaluate.h declares (checked by tests/test_evaluate_capi.py).
 EXPORTED_EVALUATE = ("lsm_head_evaluate_scratch_bytes", "lsm_head_evaluate", "lsm_host_head_evaluate")
+# Every symbol include/lsm_loss.h declares (checked by tests/test_loss_capi.py).
+EXPORTED_LOSS = ("lsm_ppo_loss_scratch_bytes", "lsm_ppo_loss", "lsm_host_ppo_loss", "lsm_loss_last_error")
+LSM_LOSS_GROUP = 256
 
 
 class LsmConfig(C.Structure):
@@ -158,6 +161,21 @@ class LsmEvalIo(C.Structure):
                                           "features", "rnn_out", "scratch", "bad")]
 
 
+class LsmLossConfig(C.Structure):
+    """lsm_loss_config (include/lsm_loss.h), passed by value."""
+    _fields_ = ([("vn_beta", C.c_double)] +
+                [(n, C.c_float) for n in ("clip_param", "huber_delta", "value_loss_coef", "entropy_coef")] +
+                [(n, C.c_int32) for n in ("use_clipped_value_loss", "use_huber_loss", "use_value_active_masks",
+                                          "use_policy_active_masks", "use_valuenorm", "num_actions")])
+
+
+class LsmLossIo(C.Structure):
+    """lsm_loss_io (include/lsm_loss.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "actions", "available_actions", "old_log_probs", "advantages",
+                                          "active_masks", "values", "value_preds", "returns", "vn_state", "denorm",
+                                          "dlogits", "dvalues", "imp_weights", "stats", "scratch", "bad")]
+
+
 class LsmError(RuntimeError):
     pass
 
@@ -248,6 +266,11 @@ def load_library(path: str = LIB_PATH):
         "lsm_head_evaluate_scratch_bytes": (SZ, [I64, I32]),
         "lsm_head_evaluate": (I32, [LsmHeadConfig, P, C.POINTER(LsmEvalIo), I64, I32, P]),
         "lsm_host_head_evaluate": (I32, [LsmHeadConfig, P, C.POINTER(LsmEvalIo), I64, I32]),
+        # include/lsm_loss.h
+        "lsm_ppo_loss_scratch_bytes": (SZ, [I64]),
+        "lsm_ppo_loss": (I32, [LsmLossConfig, C.POINTER(LsmLossIo), I64, P]),
+        "lsm_host_ppo_loss": (I32, [LsmLossConfig, C.POINTER(LsmLossIo), I64]),
+        "lsm_loss_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

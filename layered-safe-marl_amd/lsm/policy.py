@@ -12,8 +12,9 @@ synchronisation and, with a replay buffer, no torch op besides the draw of the u
 evaluation loop). ``PolicyHead.evaluate`` and ``DevicePolicy.evaluate_actions`` are the sequence form
 (``csrc/lsm_evaluate.hip`` through ``include/lsm_evaluate.h``): on a minibatch of ``recurrent_generator`` or
 ``feed_forward_generator`` the GRU state is carried through each chunk's steps, and the log-probability of
-the stored action, the entropy and the values come back. Forward passes only: no backward pass, Discrete
-action spaces only, and no CPU fallback, as elsewhere in the project.
+the stored action, the entropy and the values come back. ``DevicePolicy.ppo_loss`` adds the PPO loss and its
+gradient at the logits and the values (``lsm.loss``). No backward pass through the networks, Discrete action
+spaces only, and no CPU fallback, as elsewhere in the project.
 
 Sampling is ``Categorical.sample`` as a distribution -- the inverse CDF of ``torch.rand`` uniforms -- not
 torch's generator stream: the same seed does not reproduce ``torch.multinomial``'s actions.
@@ -296,7 +297,7 @@ class PolicyHead:
         return out
 
     def evaluate(self, x0, x1, rnn_states, masks, T, actions=None, available_actions=None, active_masks=None,
-                 check: bool = False):
+                 check: bool = False, logits: bool = False):
         """The sequence form (include/lsm_evaluate.h) on a time-major minibatch of C chunks of T steps, as
         recurrent_generator yields it: x0 [T*C, in0] (None when in0 == 0), x1 [T*C, in1], rnn_states
         [C, recurrent_N, hidden] (each chunk's state at its first step), masks [T*C, 1] or [T*C], actions
@@ -305,8 +306,10 @@ class PolicyHead:
         tensors, cached per (C, T, stream) and valid until the next call with them:
         actor {action_log_probs [T*C, 1], entropy [T*C], dist_entropy (0-dim), features, rnn_states};
         critic {values [T*C, 1], features, rnn_states} (rnn_states [C, recurrent_N, hidden]: the state
-        after the last step, only with an RNN). check=True reads the bad-input word (one synchronisation)
-        and raises when a stored action was not an integer in [0, num_actions)."""
+        after the last step, only with an RNN). logits=True (actor): the dict also holds 'logits' [T*C,
+        num_actions], the rows after the availability mask -- what lsm.loss.PPOLoss takes; every other output is
+        the same bytes. check=True reads the bad-input word (one synchronisation) and raises when a stored
+        action was not an integer in [0, num_actions)."""
         cfg = self.cfg
         torch = _torch()
         if not isinstance(x1, torch.Tensor) or x1.dim() < 1:
@@ -345,6 +348,9 @@ class PolicyHead:
             actions = available_actions = active_masks = None
         sh = torch.cuda.current_stream(self.device).cuda_stream
         out = self._eval_outputs(Cn, T, sh)
+        keep_logits = bool(logits) and actor
+        if keep_logits and "_logits" not in out:
+            out["_logits"] = torch.empty((R, cfg.num_actions), dtype=torch.float32, device=self.device)
 
         def ptr(t):
             return t.data_ptr() if t is not None else None
@@ -352,7 +358,8 @@ class PolicyHead:
         io = capi.LsmEvalIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks), actions=ptr(actions),
                             available_actions=ptr(available_actions), active_masks=ptr(active_masks),
                             log_probs=ptr(out.get("action_log_probs")), entropy=ptr(out.get("entropy")),
-                            dist_entropy=ptr(out.get("dist_entropy")), logits=None, values=ptr(out.get("values")),
+                            dist_entropy=ptr(out.get("dist_entropy")),
+                            logits=ptr(out["_logits"]) if keep_logits else None, values=ptr(out.get("values")),
                             features=ptr(out["features"]), rnn_out=ptr(out.get("rnn_states")),
                             scratch=ptr(out.get("_scratch")), bad=self.bad.data_ptr())
         rc = self.lib.lsm_head_evaluate(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), Cn, T,
@@ -362,7 +369,7 @@ class PolicyHead:
         if check and int(self.bad.item()):
             self.bad.zero_()
             raise PolicyError("a stored action that is not an integer in [0, num_actions) reached evaluate")
-        return out
+        return dict(out, logits=out["_logits"]) if keep_logits else out
 
 
 class DevicePolicy:
@@ -482,7 +489,7 @@ class DevicePolicy:
         self.last_critic = c
         return c
 
-    def evaluate_actions(self, mb, data_chunk_length=None, check: bool = False):
+    def evaluate_actions(self, mb, data_chunk_length=None, check: bool = False, logits: bool = False):
         """GR_MAPPOPolicy.evaluate_actions on one minibatch: a dict yielded by
         DeviceGraphBuffer.recurrent_generator (data_chunk_length: the generator's) or by
         feed_forward_generator (data_chunk_length None; the learner adds its own 'actions' rows, and
@@ -492,7 +499,8 @@ class DevicePolicy:
         critic's first input block is mb['share_obs'] or mb['obs'], whichever has its width.
 
         Returns device tensors, valid until the next call: values [L*C, 1], action_log_probs [L*C, 1],
-        dist_entropy (0-dim; weighted by mb['active_masks'] when the batch has them) and entropy [L*C]."""
+        dist_entropy (0-dim; weighted by mb['active_masks'] when the batch has them) and entropy [L*C];
+        with logits=True also logits [L*C, num_actions] (one more store in the actor's launch)."""
         ah, ch = self.actor_head.cfg, self.critic_head.cfg
         if mb.get("adj") is None:
             raise PolicyError("the minibatch has no dense adj (edges=True): the encoder reads the [B, E, E] matrix")
@@ -514,9 +522,39 @@ class DevicePolicy:
         a_feat = self.actor_encoder.forward(mb["node_obs"], mb["adj"], mb["agent_id"])
         a = self.actor_head.evaluate(obs, a_feat, mb.get("rnn_states"), mb.get("masks"), T, actions=mb["actions"],
                                      available_actions=mb.get("available_actions"),
-                                     active_masks=mb.get("active_masks"), check=check)
+                                     active_masks=mb.get("active_masks"), check=check, logits=logits)
         c_feat = self.critic_encoder.forward(mb["node_obs"], mb["adj"], mb["agent_id"])
         c = self.critic_head.evaluate(cent, c_feat, mb.get("rnn_states_critic"), mb.get("masks"), T)
         self.last_actor, self.last_critic = a, c
-        return {"values": c["values"], "action_log_probs": a["action_log_probs"], "dist_entropy": a["dist_entropy"],
-                "entropy": a["entropy"]}
+        out = {"values": c["values"], "action_log_probs": a["action_log_probs"], "dist_entropy": a["dist_entropy"],
+               "entropy": a["entropy"]}
+        if logits:
+            out["logits"] = a["logits"]
+        return out
+
+    def ppo_loss(self, mb, loss, value_norm=None, data_chunk_length=None, update_actor: bool = True,
+                 check: bool = False):
+        """The head of GR_MAPPO.ppo_update on one minibatch: evaluate_actions with the logits kept, then
+        `loss` (an lsm.loss.PPOLoss) on the minibatch's old_action_log_probs (or action_log_probs, as the
+        generators name the stored rows), adv_targ (or advantages), value_preds, returns and active_masks. value_norm: the
+        DeviceValueNorm that use_valuenorm updates. update_actor=False: the critic half alone, as the
+        reference's flag. Ten launches, no host synchronisation. Returns device tensors, valid until the
+        next call: policy_loss, value_loss, dist_entropy, ratio (0-dim), imp_weights [L*C, 1], dlogits
+        [L*C, num_actions], dvalues [L*C, 1] -- the seeds of torch.autograd.backward([logits, values],
+        [dlogits, dvalues]) -- and the forward's logits, values and action_log_probs."""
+        def first(*names):
+            for k in names:
+                if mb.get(k) is not None:
+                    return mb[k]
+            raise PolicyError("the minibatch has none of %s" % " / ".join(names))
+
+        if loss.cfg.num_actions != self.actor_head.cfg.num_actions:
+            raise PolicyError("the loss was built for %d actions, the actor head for %d"
+                              % (loss.cfg.num_actions, self.actor_head.cfg.num_actions))
+        ev = self.evaluate_actions(mb, data_chunk_length, check=check, logits=True)
+        out = loss.forward(ev["logits"] if update_actor else None, ev["values"], actions=mb["actions"],
+                           old_log_probs=first("old_action_log_probs", "action_log_probs"),
+                           advantages=first("adv_targ", "advantages"), value_preds=first("value_preds"),
+                           returns=first("returns"), active_masks=mb.get("active_masks"),
+                           available_actions=mb.get("available_actions"), value_norm=value_norm, check=check)
+        return dict(out, logits=ev["logits"], values=ev["values"], action_log_probs=ev["action_log_probs"])
