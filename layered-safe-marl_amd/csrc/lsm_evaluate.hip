@@ -279,17 +279,8 @@ int lsm_head_evaluate(lsm_head_config cfg, const float* weights, const lsm_eval_
   if (C == 0) return 0;
   const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
   const dim3 grid((unsigned)groups_of(C)), block(BLOCK);
-  // the kernel's dynamic-LDS limit is raised once per device, to a workgroup's whole LDS: the value never
-  // depends on the call, so concurrent callers with different configs cannot lower it under one another
-  static std::atomic<bool> raised[MAX_DEVICES];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return fail("no current device");
-  if (!raised[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute((const void*)eval_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            WORKGROUP_LDS_BYTES) != hipSuccess)
-      return fail("could not reserve the workgroup's LDS");
-    raised[dev].store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> raised[MAX_DEVICES];   // to a workgroup's whole LDS
+  if (const char* why = raise_lds_once(raised, (const void*)eval_kernel, WORKGROUP_LDS_BYTES)) return fail(why);
   eval_kernel<<<grid, block, lds, (hipStream_t)hip_stream>>>(n, n.w);
   if (hipGetLastError() != hipSuccess) return fail("launch failed");
   if (n.io.dist_entropy) {

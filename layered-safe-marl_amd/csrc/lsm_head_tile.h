@@ -11,6 +11,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -36,6 +37,20 @@ constexpr int WAVES = BLOCK / TILE;
 constexpr int MAX_IN = 256, MAX_HIDDEN = 128, MAX_LAYERS = 4, MAX_RNN = 2, MAX_ACTIONS = 64;
 constexpr int MAX_DEVICES = 64;
 constexpr int WORKGROUP_LDS_BYTES = 163840;   // 160 KB: what one workgroup can have
+
+// Raise kernel's dynamic-LDS limit to bytes, once per device (raised: the caller's own static flags, one set
+// per kernel). bytes is the kernel's worst case and never depends on the call, so concurrent callers with
+// different configs cannot lower it under one another. Returns nullptr, or the refusal's text.
+inline const char* raise_lds_once(std::atomic<bool> (&raised)[MAX_DEVICES], const void* kernel, int bytes,
+                                  const char* refused = "could not reserve the workgroup's LDS") {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return "no current device";
+  if (!raised[dev].load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return refused;
+    raised[dev].store(true, std::memory_order_release);
+  }
+  return nullptr;
+}
 
 // the head's shape and the offsets of its weights in the packed blob
 struct Shape {

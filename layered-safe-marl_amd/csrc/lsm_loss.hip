@@ -455,17 +455,10 @@ int lsm_ppo_loss(lsm_loss_config cfg, const lsm_loss_io* io, int64_t M, void* hi
   Loss n;
   if (make_loss(cfg, io, M, &n)) return 1;
   if (M == 0) return 0;
-  // the rows kernel's dynamic-LDS limit is raised once per device to what A = 64 needs: the value never
-  // depends on the call, so concurrent callers with different A cannot lower it under one another
-  static std::atomic<bool> raised[MAX_DEVICES];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return fail("no current device");
-  if (!raised[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute((const void*)rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS_BYTES) !=
-        hipSuccess)
-      return fail("could not reserve the rows kernel's LDS");
-    raised[dev].store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> raised[MAX_DEVICES];   // the rows kernel's, to what A = 64 needs
+  if (const char* why = raise_lds_once(raised, (const void*)rows_kernel, MAX_LDS_BYTES,
+                                       "could not reserve the rows kernel's LDS"))
+    return fail(why);
   const hipStream_t st = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)n.groups), block(BLOCK);
   pre_kernel<<<grid, block, 0, st>>>(n);

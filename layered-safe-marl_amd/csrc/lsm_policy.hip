@@ -229,17 +229,8 @@ int lsm_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_i
   const size_t lds = (size_t)TILE * (n.SX + 2 * n.SA) * sizeof(float);
   if (lds > (size_t)MAX_TILE_BYTES) return fail("the tile exceeds the LDS of one workgroup");
   const dim3 grid((unsigned)((M + TILE - 1) / TILE)), block(BLOCK);
-  // the kernel's dynamic-LDS limit is raised once per device, to the limits' worst case: the value never
-  // depends on the call, so concurrent callers with different configs cannot lower it under one another
-  static std::atomic<bool> raised[MAX_DEVICES];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return fail("no current device");
-  if (!raised[dev].load(std::memory_order_acquire)) {
-    if (hipFuncSetAttribute((const void*)head_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_TILE_BYTES) !=
-        hipSuccess)
-      return fail("could not reserve the workgroup's LDS");
-    raised[dev].store(true, std::memory_order_release);
-  }
+  static std::atomic<bool> raised[MAX_DEVICES];   // to the limits' worst case
+  if (const char* why = raise_lds_once(raised, (const void*)head_kernel, MAX_TILE_BYTES)) return fail(why);
   head_kernel<<<grid, block, lds, (hipStream_t)hip_stream>>>(n, n.w);
   return hipGetLastError() == hipSuccess ? 0 : fail("launch failed");
 }

@@ -24,15 +24,11 @@ from __future__ import annotations
 import ctypes as C
 
 from . import capi
+from ._device import _torch
 
 
 class EdgeError(RuntimeError):
     pass
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _check(rc, lib):

@@ -23,6 +23,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import capi
+from ._device import DeviceOp, OutputCache, _torch, pack_entries, unpack_entries
 
 AGGR = {"node": capi.LSM_GNN_NODE, "global_mean": capi.LSM_GNN_GLOBAL_MEAN, "global_max": capi.LSM_GNN_GLOBAL_MAX,
         "global_add": capi.LSM_GNN_GLOBAL_ADD}
@@ -30,11 +31,6 @@ AGGR = {"node": capi.LSM_GNN_NODE, "global_mean": capi.LSM_GNN_GLOBAL_MEAN, "glo
 
 class GnnError(RuntimeError):
     pass
-
-
-def _torch():
-    import torch
-    return torch
 
 
 @dataclass(frozen=True)
@@ -119,40 +115,17 @@ def pack_weights(state_dict, cfg: GnnConfig, prefix: str = "gnn.") -> np.ndarray
     """The packed float32 blob of a GNNBase state dict (tensors or arrays). Every entry's shape is
     checked against cfg; a missing or mis-shaped one is refused by name. Without layer norm the state
     dict has no layer_norm entries (nn.Identity) and the blob's unread gamma / beta are 1 / 0."""
-    parts = []
-    for name, shape in weight_entries(cfg):
-        key = prefix + name
-        if key not in state_dict:
-            if ".layer_norm." in name and not cfg.layer_norm:
-                parts.append(np.full(shape, 1.0 if name.endswith("weight") else 0.0, np.float32).reshape(-1))
-                continue
-            raise GnnError("pack_weights: %s is missing from the state dict" % key)
-        v = state_dict[key]
-        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
-        if tuple(a.shape) != shape:
-            raise GnnError("pack_weights: %s has shape %s, the config needs %s" % (key, tuple(a.shape), shape))
-        parts.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
-    blob = np.concatenate(parts)
-    if blob.size != weights_floats(cfg):
-        raise GnnError("pack_weights: %d floats packed, the library expects %d" % (blob.size, weights_floats(cfg)))
-    return blob
+    return pack_entries(state_dict, weight_entries(cfg), prefix, None if cfg.layer_norm else ".layer_norm.",
+                        lambda: weights_floats(cfg), GnnError, "pack_weights")
 
 
 def unpack_weights(blob, cfg: GnnConfig, prefix: str = "gnn."):
     """The inverse of pack_weights: {name: float32 array} (layer_norm entries only with layer norm)."""
-    blob = np.asarray(blob, dtype=np.float32).reshape(-1)
-    if blob.size != weights_floats(cfg):
-        raise GnnError("unpack_weights: blob of %d floats, the config needs %d" % (blob.size, weights_floats(cfg)))
-    out, o = {}, 0
-    for name, shape in weight_entries(cfg):
-        n = int(np.prod(shape))
-        if cfg.layer_norm or ".layer_norm." not in name:
-            out[prefix + name] = blob[o:o + n].reshape(shape).copy()
-        o += n
-    return out
+    return unpack_entries(blob, weight_entries(cfg), prefix, None if cfg.layer_norm else ".layer_norm.",
+                          lambda: weights_floats(cfg), GnnError, "unpack_weights")
 
 
-class GraphEncoder:
+class GraphEncoder(DeviceOp):
     """GNNBase.forward on the GPU for one config and one weight blob.
 
     The output tensor is preallocated per (B, stream) and is valid until the next call with that B on
@@ -160,47 +133,20 @@ class GraphEncoder:
     entity type or an agent_id was out of range; by default the word is not read."""
 
     def __init__(self, cfg: GnnConfig, weights, device):
-        torch = _torch()
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise GnnError("GraphEncoder needs a CUDA (HIP) device; there is no CPU fallback")
-        self.lib = capi.load_library()
+        super().__init__(device, GnnError, "GraphEncoder", "encoder")
         self._struct = cfg.struct()
-        self._n = weights_floats(cfg)
-        self.weights = torch.empty(self._n, dtype=torch.float32, device=self.device)
-        self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._out = {}
-        self._set(weights)
-
-    def _set(self, blob):
-        torch = _torch()
-        if isinstance(blob, torch.Tensor):
-            src = blob.detach().reshape(-1).to(torch.float32)
-        else:
-            src = torch.from_numpy(np.ascontiguousarray(blob, dtype=np.float32).reshape(-1))
-        if src.numel() != self._n:
-            raise GnnError("weight blob of %d floats, the config needs %d" % (src.numel(), self._n))
-        self.weights.copy_(src, non_blocking=True)   # the one device copy, on the current stream
+        self._out = OutputCache()
+        self._alloc_weights(weights_floats(cfg), weights)
 
     def load(self, state_dict, prefix: str = "gnn."):
         """Refresh the blob from a GNNBase state dict (after each optimiser step)."""
         self._set(pack_weights(state_dict, self.cfg, prefix))
 
-    def _tensor(self, t, name, dtype, shape):
-        torch = _torch()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise GnnError("%s must be a CUDA (HIP) tensor; there is no CPU fallback" % name)
-        if t.device != self.device:
-            raise GnnError("%s is on %s, the encoder on %s" % (name, t.device, self.device))
-        if t.dtype != dtype or tuple(t.shape) != tuple(shape):
-            raise GnnError("%s must be %s %s, got %s %s" % (name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-        return t if t.is_contiguous() else t.contiguous()
-
     def _run(self, node_obs, adj, masks, B, E, N, agent_id, check):
         torch = _torch()
         cfg = self.cfg
-        node_obs = self._tensor(node_obs, "node_obs", torch.float32, (B, E, cfg.F))
+        node_obs = self._tensor(node_obs, "node_obs", shape=(B, E, cfg.F))
         aid = None
         if cfg.aggr == "node":
             if agent_id is None:
@@ -213,23 +159,15 @@ class GraphEncoder:
             if aid.dtype != torch.int64:
                 aid = aid.long()   # GNNBase.forward: agent_id.long()
             aid = aid.contiguous()
-        sh = torch.cuda.current_stream(self.device).cuda_stream
-        out = self._out.get((B, sh))
-        if out is None:
-            if len(self._out) >= 8:
-                self._out.clear()
-            out = self._out[(B, sh)] = torch.empty((B, cfg.out_dim), dtype=torch.float32, device=self.device)
+        sh = self._stream()
+        out = self._out.get((B, sh), lambda: torch.empty((B, cfg.out_dim), dtype=torch.float32, device=self.device))
         rc = self.lib.lsm_gnn_forward(self._struct, C.c_void_p(self.weights.data_ptr()),
                                       C.c_void_p(node_obs.data_ptr()), C.c_void_p(adj.data_ptr()),
                                       C.c_void_p(masks.data_ptr()) if masks is not None else None, B, E, N,
                                       C.c_void_p(aid.data_ptr()) if aid is not None else None,
                                       C.c_void_p(out.data_ptr()), C.c_void_p(self.bad.data_ptr()), C.c_void_p(sh))
-        if rc != 0:
-            raise GnnError(self.lib.lsm_gnn_last_error().decode())
-        if check and int(self.bad.item()):
-            self.bad.zero_()
-            raise GnnError("an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the "
-                           "encoder")
+        self._finish(rc, self.lib.lsm_gnn_last_error, check,
+                     "an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the encoder")
         return out
 
     def forward(self, node_obs, adj, agent_id=None, check: bool = False):
@@ -238,7 +176,7 @@ class GraphEncoder:
         if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
             raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
         B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
-        adj = self._tensor(adj, "adj", torch.float32, (B, E, E))
+        adj = self._tensor(adj, "adj", shape=(B, E, E))
         return self._run(node_obs, adj, None, B, E, 1, agent_id, check)
 
     def forward_compact(self, node_obs, table, masks, num_agents: int, agent_id=None, check: bool = False):
@@ -251,10 +189,10 @@ class GraphEncoder:
         N = int(num_agents)
         if N < 1 or B % N:
             raise GnnError("node_obs holds %d graphs, not a multiple of num_agents = %d" % (B, N))
-        table = self._tensor(table, "table", torch.float32, (B // N, E, E))
+        table = self._tensor(table, "table", shape=(B // N, E, E))
         if not isinstance(masks, torch.Tensor) or masks.numel() != B * ((E + 63) // 64):
             raise GnnError("masks must hold [n * N, ceil(E / 64)] words")
-        masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", torch.int64, (B, (E + 63) // 64))
+        masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", dtype=torch.int64, shape=(B, (E + 63) // 64))
         return self._run(node_obs, table, masks, B, E, N, agent_id, check)
 
     def forward_step(self, node_obs, adj, adj_mask, num_agents: int, agent_id=None, check: bool = False):

@@ -16,6 +16,7 @@ import ctypes as C
 from dataclasses import dataclass
 
 from . import capi
+from ._device import DeviceOp, OutputCache, _torch, ptr
 
 STATS = ("policy_loss", "value_loss", "dist_entropy", "ratio")
 VN_KEYS = ("running_mean", "running_mean_sq", "debiasing_term")
@@ -23,11 +24,6 @@ VN_KEYS = ("running_mean", "running_mean_sq", "debiasing_term")
 
 class LossError(RuntimeError):
     pass
-
-
-def _torch():
-    import torch
-    return torch
 
 
 @dataclass(frozen=True)
@@ -108,47 +104,25 @@ class DeviceValueNorm:
         self.denorm.copy_(torch.cat([torch.sqrt(var), mean]))
 
 
-class PPOLoss:
+class PPOLoss(DeviceOp):
     """The loss on the GPU for one config. forward() returns a dict of device tensors preallocated per
     (M, stream), valid until the next call with that M on that stream."""
 
     def __init__(self, cfg: LossConfig, device):
-        torch = _torch()
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise LossError("PPOLoss needs a CUDA (HIP) device; there is no CPU fallback")
-        self.lib = capi.load_library()
+        super().__init__(device, LossError, "PPOLoss", "loss")
         self._struct = cfg.struct()
-        self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._out = {}
+        self._out = OutputCache()
 
-    def _tensor(self, t, name, numel):
+    def _outputs(self, M):
         torch = _torch()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise LossError("%s must be a CUDA (HIP) tensor; there is no CPU fallback" % name)
-        if t.device != self.device:
-            raise LossError("%s is on %s, the loss on %s" % (name, t.device, self.device))
-        if t.dtype != torch.float32 or t.numel() != numel:
-            raise LossError("%s must hold %d float32 values, got %s %s" % (name, numel, t.dtype, tuple(t.shape)))
-        t = t.detach()
-        return t if t.is_contiguous() else t.contiguous()
-
-    def _outputs(self, M, sh):
-        torch = _torch()
-        out = self._out.get((M, sh))
-        if out is None:
-            if len(self._out) >= 8:
-                self._out.clear()
-            dev, f32, A = self.device, torch.float32, self.cfg.num_actions
-            nbytes = int(self.lib.lsm_ppo_loss_scratch_bytes(M))
-            out = {"dlogits": torch.empty((M, A), dtype=f32, device=dev),
-                   "dvalues": torch.empty((M, 1), dtype=f32, device=dev),
-                   "imp_weights": torch.empty((M, 1), dtype=f32, device=dev),
-                   "stats": torch.empty(4, dtype=f32, device=dev),
-                   "_scratch": torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)}
-            self._out[(M, sh)] = out
-        return out
+        dev, f32, A = self.device, torch.float32, self.cfg.num_actions
+        nbytes = int(self.lib.lsm_ppo_loss_scratch_bytes(M))
+        return {"dlogits": torch.empty((M, A), dtype=f32, device=dev),
+                "dvalues": torch.empty((M, 1), dtype=f32, device=dev),
+                "imp_weights": torch.empty((M, 1), dtype=f32, device=dev),
+                "stats": torch.empty(4, dtype=f32, device=dev),
+                "_scratch": torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)}
 
     def forward(self, logits, values, actions=None, old_log_probs=None, advantages=None, value_preds=None,
                 returns=None, active_masks=None, available_actions=None, value_norm=None, check: bool = False):
@@ -159,14 +133,13 @@ class PPOLoss:
         [4]), imp_weights [M, 1], dlogits [M, A], dvalues [M, 1]}; a skipped half's entries are absent.
         Stream-ordered, no host synchronisation (check=True reads the bad-action word: one)."""
         cfg = self.cfg
-        torch = _torch()
         actor, critic = logits is not None, values is not None
         if not actor and not critic:
             raise LossError("logits and values are both None: nothing to do")
         M = (logits.numel() // cfg.num_actions) if actor else values.numel()
-        need = lambda t, name, n=M: self._tensor(t, name, n) if t is not None else None
+        need = lambda t, name, n=M: self._tensor(t, name, n, detach=True) if t is not None else None
         if actor:
-            logits = self._tensor(logits, "logits", M * cfg.num_actions)
+            logits = self._tensor(logits, "logits", M * cfg.num_actions, detach=True)
             for name, t in (("actions", actions), ("old_log_probs", old_log_probs), ("advantages", advantages)):
                 if t is None:
                     raise LossError("the actor half needs %s" % name)
@@ -180,12 +153,8 @@ class PPOLoss:
             if cfg.use_valuenorm and value_norm.device != self.device:
                 raise LossError("value_norm is on %s, the loss on %s" % (value_norm.device, self.device))
         vn = value_norm if critic and cfg.use_valuenorm else None
-        sh = torch.cuda.current_stream(self.device).cuda_stream
-        out = self._outputs(M, sh)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
+        sh = self._stream()
+        out = self._out.get((M, sh), lambda: self._outputs(M))
         io = capi.LsmLossIo(logits=ptr(logits), actions=ptr(need(actions, "actions")),
                             available_actions=ptr(available_actions) if actor else None,
                             old_log_probs=ptr(need(old_log_probs, "old_log_probs")),
@@ -198,11 +167,8 @@ class PPOLoss:
                             imp_weights=ptr(out["imp_weights"]), stats=ptr(out["stats"]),
                             scratch=ptr(out["_scratch"]), bad=self.bad.data_ptr())
         rc = self.lib.lsm_ppo_loss(self._struct, C.byref(io), M, C.c_void_p(sh))
-        if rc != 0:
-            raise LossError(self.lib.lsm_loss_last_error().decode())
-        if check and int(self.bad.item()):
-            self.bad.zero_()
-            raise LossError("a stored action that is not an integer in [0, num_actions) reached the loss")
+        self._finish(rc, self.lib.lsm_loss_last_error, check,
+                     "a stored action that is not an integer in [0, num_actions) reached the loss")
         res = {"stats": out["stats"]}
         if actor:
             res.update(policy_loss=out["stats"][0], dist_entropy=out["stats"][2], ratio=out["stats"][3],

@@ -32,17 +32,13 @@ from typing import Optional
 import numpy as np
 
 from . import capi
+from ._device import DeviceOp, OutputCache, _torch, pack_entries, ptr, unpack_entries
 
 KINDS = {"actor": capi.LSM_HEAD_ACTOR, "critic": capi.LSM_HEAD_CRITIC}
 
 
 class PolicyError(RuntimeError):
     pass
-
-
-def _torch():
-    import torch
-    return torch
 
 
 @dataclass(frozen=True)
@@ -121,42 +117,19 @@ def pack_head_weights(state_dict, cfg: HeadConfig, prefix: str = "") -> np.ndarr
     normalisation the state dict has no base.feature_norm entries and the blob's unread gamma / beta are
     1 / 0. Entries the forward pass does not use (base.mlp.fc_h.*, gnn_base.*, PopArt's statistics) are
     ignored."""
-    parts = []
-    for name, shape in head_weight_entries(cfg):
-        key = prefix + name
-        if key not in state_dict:
-            if name.startswith("base.feature_norm.") and not cfg.feature_norm:
-                parts.append(np.full(shape, 1.0 if name.endswith("weight") else 0.0, np.float32))
-                continue
-            raise PolicyError("pack_head_weights: %s is missing from the state dict" % key)
-        v = state_dict[key]
-        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
-        if tuple(a.shape) != shape:
-            raise PolicyError("pack_head_weights: %s has shape %s, the config needs %s" % (key, tuple(a.shape), shape))
-        parts.append(np.ascontiguousarray(a, dtype=np.float32).reshape(-1))
-    blob = np.concatenate(parts)
-    if blob.size != head_weights_floats(cfg):
-        raise PolicyError("pack_head_weights: %d floats packed, the library expects %d"
-                          % (blob.size, head_weights_floats(cfg)))
-    return blob
+    return pack_entries(state_dict, head_weight_entries(cfg), prefix,
+                        None if cfg.feature_norm else "base.feature_norm.", lambda: head_weights_floats(cfg),
+                        PolicyError, "pack_head_weights")
 
 
 def unpack_head_weights(blob, cfg: HeadConfig, prefix: str = ""):
     """The inverse of pack_head_weights: {name: float32 array} (feature_norm entries only with it on)."""
-    blob = np.asarray(blob, dtype=np.float32).reshape(-1)
-    if blob.size != head_weights_floats(cfg):
-        raise PolicyError("unpack_head_weights: blob of %d floats, the config needs %d"
-                          % (blob.size, head_weights_floats(cfg)))
-    out, o = {}, 0
-    for name, shape in head_weight_entries(cfg):
-        n = int(np.prod(shape))
-        if cfg.feature_norm or not name.startswith("base.feature_norm."):
-            out[prefix + name] = blob[o:o + n].reshape(shape).copy()
-        o += n
-    return out
+    return unpack_entries(blob, head_weight_entries(cfg), prefix,
+                          None if cfg.feature_norm else "base.feature_norm.", lambda: head_weights_floats(cfg),
+                          PolicyError, "unpack_head_weights")
 
 
-class PolicyHead:
+class PolicyHead(DeviceOp):
     """One head on the GPU for one config and one weight blob.
 
     forward() returns a dict of output tensors preallocated per (M, stream), valid until the next call
@@ -164,61 +137,57 @@ class PolicyHead:
     raises when a uniform was not in [0, 1); by default the word is not read."""
 
     def __init__(self, cfg: HeadConfig, weights, device):
-        torch = _torch()
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise PolicyError("PolicyHead needs a CUDA (HIP) device; there is no CPU fallback")
-        self.lib = capi.load_library()
+        super().__init__(device, PolicyError, "PolicyHead", "head")
         self._struct = cfg.struct()
-        self._n = head_weights_floats(cfg)
-        self.weights = torch.empty(self._n, dtype=torch.float32, device=self.device)
-        self.bad = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self._out = {}
-        self._eval_out = {}
-        self._set(weights)
-
-    def _set(self, blob):
-        torch = _torch()
-        if isinstance(blob, torch.Tensor):
-            src = blob.detach().reshape(-1).to(torch.float32)
-        else:
-            src = torch.from_numpy(np.ascontiguousarray(blob, dtype=np.float32).reshape(-1))
-        if src.numel() != self._n:
-            raise PolicyError("weight blob of %d floats, the config needs %d" % (src.numel(), self._n))
-        self.weights.copy_(src, non_blocking=True)   # the one device copy, on the current stream
+        self._out = OutputCache()
+        self._eval_out = OutputCache()
+        self._alloc_weights(head_weights_floats(cfg), weights)
 
     def load(self, state_dict, prefix: str = ""):
         """Refresh the blob from a GR_Actor / GR_Critic state dict (after each optimiser step)."""
         self._set(pack_head_weights(state_dict, self.cfg, prefix))
 
-    def _tensor(self, t, name, numel):
-        torch = _torch()
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise PolicyError("%s must be a CUDA (HIP) tensor; there is no CPU fallback" % name)
-        if t.device != self.device:
-            raise PolicyError("%s is on %s, the head on %s" % (name, t.device, self.device))
-        if t.dtype != torch.float32 or t.numel() != numel:
-            raise PolicyError("%s must hold %d float32 values, got %s %s" % (name, numel, t.dtype, tuple(t.shape)))
-        return t if t.is_contiguous() else t.contiguous()
+    def _inputs(self, x0, x1, rnn_states, masks, T, shape, who):
+        """forward's and evaluate's (R, x0, x1, rnn_states, masks) after their checks: R rows, taken from x1,
+        in chunks of T steps (forward: 1) with one row of GRU state each. shape and who are the caller's
+        words in the refusals."""
+        cfg = self.cfg
+        if not isinstance(x1, self._torch.Tensor) or x1.dim() < 1:
+            raise PolicyError("x1 must be a CUDA (HIP) tensor %s; there is no CPU fallback" % shape)
+        if cfg.in1 < 1:
+            raise PolicyError("%s takes the row count from x1: the config needs in1 >= 1" % who)
+        R = x1.numel() // cfg.in1
+        if T < 1 or R % T:
+            raise PolicyError("%d rows are not chunks of T = %d steps" % (R, T))
+        x1 = self._tensor(x1, "x1", R * cfg.in1)
+        if cfg.in0:
+            if x0 is None:
+                raise PolicyError("the head was built with in0 = %d: x0 is needed" % cfg.in0)
+            x0 = self._tensor(x0, "x0", R * cfg.in0)
+        else:
+            x0 = None
+        if cfg.recurrent_N:
+            if rnn_states is None or masks is None:
+                raise PolicyError("a recurrent head needs rnn_states and masks")
+            rnn_states = self._tensor(rnn_states, "rnn_states", R // T * cfg.recurrent_N * cfg.hidden)
+            masks = self._tensor(masks, "masks", R)
+        else:
+            rnn_states = masks = None
+        return R, x0, x1, rnn_states, masks
 
-    def _outputs(self, M, sh):
+    def _outputs(self, M):
         torch = _torch()
-        out = self._out.get((M, sh))
-        if out is None:
-            if len(self._out) >= 8:
-                self._out.clear()
-            cfg, dev, f32 = self.cfg, self.device, torch.float32
-            out = {"features": torch.empty((M, cfg.hidden), dtype=f32, device=dev)}
-            if cfg.recurrent_N:
-                out["rnn_states"] = torch.empty((M, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
-            if cfg.kind == "actor":
-                out["actions_env"] = torch.empty((M,), dtype=torch.int32, device=dev)
-                out["actions"] = torch.empty((M, 1), dtype=f32, device=dev)
-                out["action_log_probs"] = torch.empty((M, 1), dtype=f32, device=dev)
-            else:
-                out["values"] = torch.empty((M, 1), dtype=f32, device=dev)
-            self._out[(M, sh)] = out
+        cfg, dev, f32 = self.cfg, self.device, torch.float32
+        out = {"features": torch.empty((M, cfg.hidden), dtype=f32, device=dev)}
+        if cfg.recurrent_N:
+            out["rnn_states"] = torch.empty((M, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
+        if cfg.kind == "actor":
+            out["actions_env"] = torch.empty((M,), dtype=torch.int32, device=dev)
+            out["actions"] = torch.empty((M, 1), dtype=f32, device=dev)
+            out["action_log_probs"] = torch.empty((M, 1), dtype=f32, device=dev)
+        else:
+            out["values"] = torch.empty((M, 1), dtype=f32, device=dev)
         return out
 
     def forward(self, x0, x1, rnn_states=None, masks=None, u=None, available_actions=None, check: bool = False):
@@ -227,37 +196,14 @@ class PolicyHead:
         Actor: {actions_env int32 [M], actions [M, 1], action_log_probs [M, 1], features, rnn_states};
         critic: {values [M, 1], features, rnn_states} (rnn_states only with an RNN)."""
         cfg = self.cfg
-        torch = _torch()
-        if not isinstance(x1, torch.Tensor) or x1.dim() < 1:
-            raise PolicyError("x1 must be a CUDA (HIP) tensor [M, in1]; there is no CPU fallback")
-        if cfg.in1 < 1:
-            raise PolicyError("PolicyHead.forward takes the row count from x1: the config needs in1 >= 1")
-        M = x1.numel() // cfg.in1
-        x1 = self._tensor(x1, "x1", M * cfg.in1)
-        if cfg.in0:
-            if x0 is None:
-                raise PolicyError("the head was built with in0 = %d: x0 is needed" % cfg.in0)
-            x0 = self._tensor(x0, "x0", M * cfg.in0)
-        else:
-            x0 = None
-        if cfg.recurrent_N:
-            if rnn_states is None or masks is None:
-                raise PolicyError("a recurrent head needs rnn_states and masks")
-            rnn_states = self._tensor(rnn_states, "rnn_states", M * cfg.recurrent_N * cfg.hidden)
-            masks = self._tensor(masks, "masks", M)
-        else:
-            rnn_states = masks = None
+        M, x0, x1, rnn_states, masks = self._inputs(x0, x1, rnn_states, masks, 1, "[M, in1]", "PolicyHead.forward")
         actor = cfg.kind == "actor"
         if actor and u is not None:
             u = self._tensor(u, "u", M)
         if actor and available_actions is not None:
             available_actions = self._tensor(available_actions, "available_actions", M * cfg.num_actions)
-        sh = torch.cuda.current_stream(self.device).cuda_stream
-        out = self._outputs(M, sh)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
+        sh = self._stream()
+        out = self._out.get((M, sh), lambda: self._outputs(M))
         io = capi.LsmHeadIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks),
                             u=ptr(u) if actor else None, available_actions=ptr(available_actions) if actor else None,
                             actions_i32=ptr(out.get("actions_env")), actions_f32=ptr(out.get("actions")),
@@ -266,34 +212,25 @@ class PolicyHead:
                             bad=self.bad.data_ptr())
         rc = self.lib.lsm_head_forward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), M,
                                        C.c_void_p(sh))
-        if rc != 0:
-            raise PolicyError(self.lib.lsm_policy_last_error().decode())
-        if check and int(self.bad.item()):
-            self.bad.zero_()
-            raise PolicyError("a uniform outside [0, 1) reached the sampler")
+        self._finish(rc, self.lib.lsm_policy_last_error, check, "a uniform outside [0, 1) reached the sampler")
         return out
 
     __call__ = forward
 
-    def _eval_outputs(self, Cn, T, sh):
+    def _eval_outputs(self, Cn, T):
         torch = _torch()
-        out = self._eval_out.get((Cn, T, sh))
-        if out is None:
-            if len(self._eval_out) >= 8:
-                self._eval_out.clear()
-            cfg, dev, f32, R = self.cfg, self.device, torch.float32, Cn * T
-            out = {"features": torch.empty((R, cfg.hidden), dtype=f32, device=dev)}
-            if cfg.recurrent_N:
-                out["rnn_states"] = torch.empty((Cn, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
-            if cfg.kind == "actor":
-                out["action_log_probs"] = torch.empty((R, 1), dtype=f32, device=dev)
-                out["entropy"] = torch.empty((R,), dtype=f32, device=dev)
-                out["dist_entropy"] = torch.empty((), dtype=f32, device=dev)
-                nbytes = int(self.lib.lsm_head_evaluate_scratch_bytes(Cn, T))
-                out["_scratch"] = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
-            else:
-                out["values"] = torch.empty((R, 1), dtype=f32, device=dev)
-            self._eval_out[(Cn, T, sh)] = out
+        cfg, dev, f32, R = self.cfg, self.device, torch.float32, Cn * T
+        out = {"features": torch.empty((R, cfg.hidden), dtype=f32, device=dev)}
+        if cfg.recurrent_N:
+            out["rnn_states"] = torch.empty((Cn, cfg.recurrent_N, cfg.hidden), dtype=f32, device=dev)
+        if cfg.kind == "actor":
+            out["action_log_probs"] = torch.empty((R, 1), dtype=f32, device=dev)
+            out["entropy"] = torch.empty((R,), dtype=f32, device=dev)
+            out["dist_entropy"] = torch.empty((), dtype=f32, device=dev)
+            nbytes = int(self.lib.lsm_head_evaluate_scratch_bytes(Cn, T))
+            out["_scratch"] = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=dev)
+        else:
+            out["values"] = torch.empty((R, 1), dtype=f32, device=dev)
         return out
 
     def evaluate(self, x0, x1, rnn_states, masks, T, actions=None, available_actions=None, active_masks=None,
@@ -311,30 +248,9 @@ class PolicyHead:
         the same bytes. check=True reads the bad-input word (one synchronisation) and raises when a stored
         action was not an integer in [0, num_actions)."""
         cfg = self.cfg
-        torch = _torch()
-        if not isinstance(x1, torch.Tensor) or x1.dim() < 1:
-            raise PolicyError("x1 must be a CUDA (HIP) tensor [T*C, in1]; there is no CPU fallback")
-        if cfg.in1 < 1:
-            raise PolicyError("PolicyHead.evaluate takes the row count from x1: the config needs in1 >= 1")
         T = 1 if T is None else int(T)
-        R = x1.numel() // cfg.in1
-        if T < 1 or R % T:
-            raise PolicyError("%d rows are not chunks of T = %d steps" % (R, T))
+        R, x0, x1, rnn_states, masks = self._inputs(x0, x1, rnn_states, masks, T, "[T*C, in1]", "PolicyHead.evaluate")
         Cn = R // T
-        x1 = self._tensor(x1, "x1", R * cfg.in1)
-        if cfg.in0:
-            if x0 is None:
-                raise PolicyError("the head was built with in0 = %d: x0 is needed" % cfg.in0)
-            x0 = self._tensor(x0, "x0", R * cfg.in0)
-        else:
-            x0 = None
-        if cfg.recurrent_N:
-            if rnn_states is None or masks is None:
-                raise PolicyError("a recurrent head needs rnn_states and masks")
-            rnn_states = self._tensor(rnn_states, "rnn_states", Cn * cfg.recurrent_N * cfg.hidden)
-            masks = self._tensor(masks, "masks", R)
-        else:
-            rnn_states = masks = None
         actor = cfg.kind == "actor"
         if actor:
             if actions is None:
@@ -346,15 +262,12 @@ class PolicyHead:
                 active_masks = self._tensor(active_masks, "active_masks", R)
         else:
             actions = available_actions = active_masks = None
-        sh = torch.cuda.current_stream(self.device).cuda_stream
-        out = self._eval_outputs(Cn, T, sh)
+        sh = self._stream()
+        out = self._eval_out.get((Cn, T, sh), lambda: self._eval_outputs(Cn, T))
         keep_logits = bool(logits) and actor
         if keep_logits and "_logits" not in out:
+            torch = _torch()
             out["_logits"] = torch.empty((R, cfg.num_actions), dtype=torch.float32, device=self.device)
-
-        def ptr(t):
-            return t.data_ptr() if t is not None else None
-
         io = capi.LsmEvalIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks), actions=ptr(actions),
                             available_actions=ptr(available_actions), active_masks=ptr(active_masks),
                             log_probs=ptr(out.get("action_log_probs")), entropy=ptr(out.get("entropy")),
@@ -364,11 +277,8 @@ class PolicyHead:
                             scratch=ptr(out.get("_scratch")), bad=self.bad.data_ptr())
         rc = self.lib.lsm_head_evaluate(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), Cn, T,
                                         C.c_void_p(sh))
-        if rc != 0:
-            raise PolicyError(self.lib.lsm_policy_last_error().decode())
-        if check and int(self.bad.item()):
-            self.bad.zero_()
-            raise PolicyError("a stored action that is not an integer in [0, num_actions) reached evaluate")
+        self._finish(rc, self.lib.lsm_policy_last_error, check,
+                     "a stored action that is not an integer in [0, num_actions) reached evaluate")
         return dict(out, logits=out["_logits"]) if keep_logits else out
 
 

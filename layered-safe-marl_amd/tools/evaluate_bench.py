@@ -19,14 +19,13 @@ minibatch of their own): the same modules in float64 are the truth, e32 is the f
 against it, and a fused error above 4 * e32 + 4 * 2^-23 * max|truth| on the features, the final state, the
 values, the log-probabilities or the entropy ends the run. Then a warm-up, HIP events on the stream around
 `reps` back-to-back calls, the sides in alternating rounds, and the median / min / max of the rounds' means
-(tools/returns_bench.py's alternated()).
+(tools/bench_common.py's alternated()).
 
     python layered-safe-marl_amd/tools/evaluate_bench.py [--out FILE] [--quick]
 """
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -35,7 +34,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
 from policy_bench import seeded_state_dict, torch_head  # noqa: E402
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, criterion, emit  # noqa: E402
 
 DEV = "cuda:0"
 OBS, ENC, HIDDEN, ACTIONS = 6, 16, 64, 25
@@ -113,18 +112,9 @@ def bench_head(role, recurrent, quick):
         r = torch_evaluate(mod64, cfg, dbl(s0), dbl(s1), dbl(ss), dbl(sm), sa, dbl(sw), nb, T)
     names = ["features"] + (["rnn_states"] if rn else [])
     names += ["action_log_probs", "entropy", "dist_entropy"] if role == "actor" else ["values"]
-    checks = {}
-    for name in names:
-        truth = r[name]
-        e32 = float((b[name].double() - truth).abs().max().item())
-        err = float((a[name].double().reshape(truth.shape) - truth).abs().max().item())
-        tol = 4.0 * e32 + 4.0 * 2.0 ** -23 * float(truth.abs().max().item())
-        if name == "dist_entropy":   # the tests' rule: the entropy's tolerance plus one rounding of the value
-            tol = checks["entropy"]["tolerance"] + 2.0 ** -23 * float(truth.abs().item())
-        checks[name] = {"fused_err_vs_float64": err, "torch_err_vs_float64": e32, "tolerance": tol}
-        if not err <= tol:
-            raise SystemExit("%s %s: fused error %g against float64 exceeds the tolerance %g (torch float32: %g)"
-                             % (role, name, err, tol, e32))
+    # the tests' rule for dist_entropy: the entropy's tolerance plus one rounding of the value
+    mean_rule = lambda checks, truth: checks["entropy"]["tolerance"] + 2.0 ** -23 * float(truth.abs().item())
+    checks = criterion(a, b, r, names, role, special={"dist_entropy": mean_rule})
     sides = {"fused": (fused, 5 if quick else 20), "torch": (plain, 2 if quick else 5)}
     for fn, _ in sides.values():   # warm-up
         fn()
@@ -143,12 +133,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="fewer calls per round")
     a = ap.parse_args()
     runs = [bench_head(role, rec, a.quick) for rec in (True, False) for role in ("actor", "critic")]
-    line = json.dumps({"evaluate_bench": runs})
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
-    print(line)
+    emit({"evaluate_bench": runs}, a.out)
 
 
 if __name__ == "__main__":

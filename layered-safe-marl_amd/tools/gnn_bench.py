@@ -16,14 +16,13 @@ the same torch ops in float64 are the truth, e32 is the float32 torch path's err
 fused error above 4 * e32 + 4 * 2^-23 * max|truth| ends the run (the two float32 results' own distance
 is recorded, not judged: at E = 192 sums over ~190 incoming edges make it a few 1e-3 of the output). Then a
 warm-up, HIP events on the stream around `reps` back-to-back calls, the sides in alternating rounds, and
-the median / min / max of the rounds' means (tools/returns_bench.py's alternated()).
+the median / min / max of the rounds' means (tools/bench_common.py's alternated()).
 
     python layered-safe-marl_amd/tools/gnn_bench.py [--out FILE] [--quick]
 """
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -31,7 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, criterion, emit  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -136,14 +135,11 @@ def bench_env(envs, agents, layout, quick):
         el = edges.process_adj(dense[:nb])
         p64 = {k: v.double() for k, v in p.items()}
         r64 = torch_forward(cfg, p64, node[:nb].double(), None, aid[:nb], (el[0], el[1].double()))
-        e32 = float((b[:nb].double() - r64).abs().max().item())
-        err = float((a[:nb].double() - r64).abs().max().item())
-        tol = 4.0 * e32 + 4.0 * 2.0 ** -23 * float(r64.abs().max().item())
         # a float64 result far outside the float32 results' range is no truth to judge by: recorded, not used
         usable = float(r64.abs().max().item()) <= 10.0 * max(1.0, scale)
-        if usable and not err <= tol:
-            raise SystemExit("%s %s: fused error %g against float64 exceeds 4 * e32 + 4 ulp = %g (torch float32: %g)"
-                             % (layout, role, err, tol, e32))
+        chk = criterion({role: a[:nb]}, {role: b[:nb]}, {role: r64}, [role], layout, bound="4 * e32 + 4 ulp =",
+                        enforce=usable)[role]
+        err, e32 = chk["fused_err_vs_float64"], chk["torch_err_vs_float64"]
         sides = {"fused": (fused, 5 if quick else 20), "torch": (plain, 1 if quick else 3)}
         if aggr == "node":
             enc_ego = gnn.GraphEncoder(gnn.GnnConfig(F=F, aggr=aggr, ego_only=True), enc.weights, DEV)
@@ -174,12 +170,7 @@ def main():
         runs += [bench_env(4096, 8, "reference", a.quick), bench_env(4096, 8, "compact", a.quick)]
     if a.only in (None, "large"):
         runs += [bench_env(128, 64, "compact", a.quick)]   # the layout bench.py's config 5 steps in
-    line = json.dumps({"gnn_bench": runs})
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
-    print(line)
+    emit({"gnn_bench": runs}, a.out)
 
 
 if __name__ == "__main__":

@@ -20,7 +20,7 @@ gradient jumps (ratio against 1 -+ clip outside it, |values - value_preds| again
 two losses against each other outside the clip) are moved off it beforehand (old_log_probs := the row's
 log-probability, value_preds := values), as the tests redraw them: float32 and float64 may resolve a near-tie
 differently. Then a warm-up, HIP events on the stream around `reps` back-to-back calls, the sides in alternating
-rounds, and the median / min / max of the rounds' means (tools/returns_bench.py's alternated()).
+rounds, and the median / min / max of the rounds' means (tools/bench_common.py's alternated()).
 
 Bytes model of (A): per row A + 8 floats read (logits, actions, old_log_probs, advantages, values, value_preds,
 returns, active_masks) and A + 1 written (dlogits, dvalues), so M * (2 A + 9) * 4 bytes, reported as a fraction of
@@ -33,7 +33,6 @@ back-to-back calls do not run cold.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -41,7 +40,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, criterion, emit  # noqa: E402
 
 DEV = "cuda:0"
 ROWS, ACTIONS, CHECK_ROWS = 512000, 25, 4096
@@ -151,16 +150,7 @@ def run(quick):
     a = {k: v.clone() for k, v in fused(slg, svl, s).items()}
     a["vn_state"] = vn.state.clone()
     b = plain(slg, svl, s)
-    checks = {}
-    for name in ("dlogits", "dvalues", "imp_weights", "stats", "vn_state"):
-        truth = r[name]
-        e32 = float((b[name].double() - truth).abs().max().item())
-        err = float((a[name].double().reshape(truth.shape) - truth).abs().max().item())
-        tol = 4.0 * e32 + 4.0 * 2.0 ** -23 * float(truth.abs().max().item())
-        checks[name] = {"fused_err_vs_float64": err, "torch_err_vs_float64": e32, "tolerance": tol}
-        if not err <= tol:
-            raise SystemExit("%s: fused error %g against float64 exceeds the tolerance %g (torch float32: %g)"
-                             % (name, err, tol, e32))
+    checks = criterion(a, b, r, ("dlogits", "dvalues", "imp_weights", "stats", "vn_state"), "")
     # ---- timing --------------------------------------------------------------------------------------------
     t["actions_f"] = t["actions"].float()
     sides = {"fused": (fused, 5 if quick else 20), "torch": (plain, 2 if quick else 5)}
@@ -183,12 +173,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="fewer calls per round")
     a = ap.parse_args()
-    line = json.dumps({"loss_bench": run(a.quick)})
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
-    print(line)
+    emit({"loss_bench": run(a.quick)}, a.out)
 
 
 if __name__ == "__main__":

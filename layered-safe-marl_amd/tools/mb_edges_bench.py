@@ -12,7 +12,7 @@ once per minibatch, for the edge count. The outputs are compared first, every mi
 generators (torch.equal on edge_index and edge_attr), and a difference ends the run. Then HIP events
 around whole passes over the buffer (16 minibatches) on an otherwise idle stream, after a warm-up; the
 sides are timed in alternating rounds and the median, minimum and maximum of the rounds' means are
-recorded (the method of tools/returns_bench.py).
+recorded (tools/bench_common.py's alternated()).
 
     python layered-safe-marl_amd/tools/mb_edges_bench.py [--envs 4096] [--steps T] [--mini-batches 16] [--out FILE]
 
@@ -25,7 +25,6 @@ own layout.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -33,7 +32,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, emit  # noqa: E402
 
 L_CHUNK, HIDDEN, ACTIONS = 10, 64, 25
 REPS = 3   # passes over the buffer per round
@@ -146,11 +145,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("mb_edges_bench needs a GPU")
     out = {layout: bench_layout(layout, a, a.steps) for layout in a.layouts.split(",")}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":

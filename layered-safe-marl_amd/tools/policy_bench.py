@@ -15,14 +15,13 @@ same modules in float64 are the truth, e32 is the float32 modules' error against
 4 * e32 + 4 * 2^-23 * max|truth| on the features, the new state, the values or the log-probability of the
 action the fused head chose ends the run. Then a warm-up, HIP events on the stream around `reps`
 back-to-back calls, the sides in alternating rounds, and the median / min / max of the rounds' means
-(tools/returns_bench.py's alternated()).
+(tools/bench_common.py's alternated()).
 
     python layered-safe-marl_amd/tools/policy_bench.py [--out FILE] [--quick]
 """
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
@@ -30,7 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, criterion, emit  # noqa: E402
 
 DEV = "cuda:0"
 M, OBS, ENC, HIDDEN, ACTIONS = 32768, 6, 16, 64, 25
@@ -142,22 +141,13 @@ def bench_head(role, quick):
     with torch.no_grad():
         r = mod64(None if x0 is None else x0[:nb].double(), x1[:nb].double(), st[:nb].double(), masks[:nb].double(),
                   sample=False)
-    checks = {}
-    pairs = [("features", a["features"], b["features"], r["features"]),
-             ("rnn_states", a["rnn_states"], b["rnn_states"], r["rnn_states"])]
+    b32 = {k: b[k][:nb] for k in ("features", "rnn_states")}
     if role == "actor":
         act = a["actions_env"].long().view(-1, 1)
-        pairs.append(("action_log_probs", a["action_log_probs"], b["logp"][:nb].gather(1, act), r["logp"].gather(1, act)))
+        b32["action_log_probs"], r["action_log_probs"] = b["logp"][:nb].gather(1, act), r["logp"].gather(1, act)
     else:
-        pairs.append(("values", a["values"], b["values"], r["values"]))
-    for name, fa, fb, truth in pairs:
-        e32 = float((fb[:nb].double() - truth).abs().max().item())
-        err = float((fa.double() - truth).abs().max().item())
-        tol = 4.0 * e32 + 4.0 * 2.0 ** -23 * float(truth.abs().max().item())
-        checks[name] = {"fused_err_vs_float64": err, "torch_err_vs_float64": e32, "tolerance": tol}
-        if not err <= tol:
-            raise SystemExit("%s %s: fused error %g against float64 exceeds 4 * e32 + 4 ulp = %g (torch float32: %g)"
-                             % (role, name, err, tol, e32))
+        b32["values"] = b["values"][:nb]
+    checks = criterion(a, b32, r, list(b32), role, bound="4 * e32 + 4 ulp =")
     if role == "actor":
         # the sampler as a distribution: the fused head's action frequencies against the float64 probabilities
         p = r["logp"].exp().mean(dim=0)
@@ -180,12 +170,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="fewer calls per round")
     a = ap.parse_args()
     runs = [bench_head("actor", a.quick), bench_head("critic", a.quick)]
-    line = json.dumps({"policy_bench": runs})
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as fh:
-            fh.write(line + "\n")
-    print(line)
+    emit({"policy_bench": runs}, a.out)
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ All three write the same 16 fields; the index construction is part of (a) and (b
 compared first (every minibatch of the 16-minibatch split and the whole-buffer minibatch) and a
 difference ends the run. HIP events around repeated calls on an otherwise idle stream, after a warm-up;
 the sides are timed in alternating rounds and the median, minimum and maximum of the rounds' means are
-recorded (the method of tools/returns_bench.py). The per-step lsm_buffer_copy_rows launch (the policy
+recorded (tools/bench_common.py's alternated()). The per-step lsm_buffer_copy_rows launch (the policy
 rows of one step, six copies) is timed the same way.
 
     python layered-safe-marl_amd/tools/recurrent_bench.py [--envs 4096] [--steps T] [--mini-batches 16] [--out FILE]
@@ -22,7 +22,6 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
@@ -30,7 +29,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
-from returns_bench import alternated  # noqa: E402
+from bench_common import alternated, emit  # noqa: E402
 
 L_CHUNK, HIDDEN, ACTIONS = 10, 64, 25
 FIRST = ("rnn_states", "rnn_states_critic")
@@ -206,11 +205,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("recurrent_bench needs a GPU")
     out = {layout: bench_layout(layout, a, a.steps) for layout in a.layouts.split(",")}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":

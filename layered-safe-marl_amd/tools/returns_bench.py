@@ -15,43 +15,17 @@ the mask words. The compact layout has no torch baseline: its samples exist only
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+
+from bench_common import alternated, emit  # noqa: E402
 
 GAMMA, LAMBDA = 0.99, 0.95
 DEN = (2.85, 2.04)
-
-
-def timed(fn, reps):
-    """Mean device milliseconds per call of fn over reps calls (events on the current stream)."""
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-ROUNDS = 7
-
-
-def alternated(sides):
-    """sides: {name: (fn, reps)}. ROUNDS rounds, each timing every side once in turn (so that drift of
-    the machine falls on all sides alike). Returns {name: {"median", "min", "max"}} of the rounds' means,
-    milliseconds per call."""
-    ms = {k: [] for k in sides}
-    for _ in range(ROUNDS):
-        for k, (fn, reps) in sides.items():
-            ms[k].append(timed(fn, reps))
-    return {k: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "reps_per_round": sides[k][1],
-                "rounds": ROUNDS} for k, v in ms.items()}
 
 
 def torch_returns_advantages(buf, next_value, den):
@@ -205,11 +179,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("returns_bench needs a GPU")
     out = {"reference": bench_layout("reference", a, a.steps), "compact": bench_layout("compact", a, a.steps)}
-    line = json.dumps(out)
-    print(line)
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(out, a.out)
 
 
 if __name__ == "__main__":

@@ -7,11 +7,11 @@ update), and get_values / act as the two halves of get_actions."""
 import numpy as np
 import pytest
 
+import device_policy_cases as dp
 import evaluate_cases as ec
 import evaluate_model as em
-import gnn_model as gm
 import policy_model as pm
-from lsm import capi, gnn, policy
+from lsm import capi, policy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -93,42 +93,6 @@ def test_device_matches_host(lib, which):
 
 # ---- the public surface ---------------------------------------------------------------------------------------
 
-def _heads(env, recurrent_N=1, seed=0):
-    """(DevicePolicy, the two head configs and state dicts) for env: the reference's default sizes."""
-    N, OBS, F = env.N, env.OBS, env.F
-    acfg, ccfg = gnn.GnnConfig(F=F, aggr="node"), gnn.GnnConfig(F=F, aggr="global_mean")
-    ah = policy.HeadConfig(kind="actor", in0=OBS, in1=16, num_actions=25, recurrent_N=recurrent_N)
-    ch = policy.HeadConfig(kind="critic", in0=N * OBS, in1=16, recurrent_N=recurrent_N)
-    asd, csd = pm.random_head_weights(ah, 11 + seed), pm.random_head_weights(ch, 12 + seed)
-    pol = policy.DevicePolicy(gnn.GraphEncoder(acfg, gm.default_weights(acfg, 5)[1], DEV),
-                              policy.PolicyHead(ah, policy.pack_head_weights(asd, ah), DEV),
-                              gnn.GraphEncoder(ccfg, gm.default_weights(ccfg, 6)[1], DEV),
-                              policy.PolicyHead(ch, policy.pack_head_weights(csd, ch), DEV))
-    return pol, (ah, asd), (ch, csd)
-
-
-def _env(layout="reference"):
-    from lsm.config import EnvArgs
-    from lsm.vec_env import GpuGraphVecEnv
-    return GpuGraphVecEnv(EnvArgs(num_agents=3, seed=1), num_envs=4, device=DEV, return_numpy=False, build_infos=False,
-                          adj_layout=layout)
-
-
-def _collect(env, pol, T):
-    """T collect steps into a DeviceGraphBuffer with policy rows."""
-    import torch
-    from lsm.buffer import DeviceGraphBuffer
-    buf = DeviceGraphBuffer(env, episode_length=T, policy_rows=dict(hidden_size=64, recurrent_N=1, act_dim=1,
-                                                                    num_actions=None))
-    buf.warmup(0)
-    g = torch.Generator(device=DEV).manual_seed(5)
-    for t in range(T):
-        out = pol.get_actions(env, buf.rnn_states[t], buf.rnn_states_critic[t], buf.masks[t], generator=g, buffer=buf)
-        buf.insert_step(out["actions_env"], 0, value_preds=out["values"],
-                        policy={k: out[k] for k in ("actions", "action_log_probs", "rnn_states", "rnn_states_critic")})
-    return buf
-
-
 def _reproduces(pol, heads, mb, L, what):
     """evaluate_actions(mb, L) against the minibatch's stored log-probabilities and values, within twice the
     tolerance of the minibatch as a case (the two models on the same inputs and encoder outputs)."""
@@ -176,9 +140,9 @@ def test_evaluate_actions_reproduces_a_collected_recurrent_minibatch(lib, layout
     agent's series) and one minibatch of 24 chunks: with unchanged weights evaluate_actions gives the stored
     old_action_log_probs and value_preds back -- importance ratio 1 before any update."""
     import torch
-    env = _env(layout)
-    pol, ah, ch = _heads(env, seed=1)
-    buf = _collect(env, pol, 6)
+    env = dp.env(layout)
+    pol, ah, ch = dp.heads(env, seed=1)
+    buf = dp.collect(env, pol, 6)
     adv = torch.zeros(6 * 4 * 3, dtype=torch.float32, device=DEV)
     batches = list(buf.recurrent_generator(adv, 1, 3))
     assert len(batches) == 1 and tuple(batches[0]["rnn_states"].shape) == (24, 1, 64)
@@ -200,10 +164,10 @@ def test_evaluate_actions_reproduces_a_collected_feed_forward_minibatch(lib):
     """The same through feed_forward_generator with non-recurrent heads: the learner gathers its own policy
     rows with the yielded indices."""
     import torch
-    env = _env()
-    pol, ah, ch = _heads(env, recurrent_N=0, seed=2)
+    env = dp.env()
+    pol, ah, ch = dp.heads(env, recurrent_N=0, seed=2)
     T = 6
-    buf = _collect(env, pol, T)
+    buf = dp.collect(env, pol, T)
     adv = torch.zeros(T * 4 * 3, dtype=torch.float32, device=DEV)
     mb = dict(next(iter(buf.feed_forward_generator(adv, num_mini_batch=1))))
     idx = mb["indices"]
@@ -232,8 +196,8 @@ def test_get_values_and_act_are_the_halves_of_get_actions(lib, with_buffer):
     the same inputs); sampled, act draws what get_actions draws from the same generator state."""
     import torch
     from lsm.buffer import DeviceGraphBuffer
-    env = _env()
-    pol, _, _ = _heads(env, seed=3)
+    env = dp.env()
+    pol, _, _ = dp.heads(env, seed=3)
     M = 12
     buf = None
     if with_buffer:

@@ -8,6 +8,7 @@ compute_returns and advantages."""
 import numpy as np
 import pytest
 
+import device_policy_cases as dp
 import evaluate_cases as ec
 import evaluate_model as em
 import loss_cases as lc
@@ -186,10 +187,9 @@ def test_ppo_loss_closes_the_loop_on_a_collected_minibatch(lib, layout):
     the four scalars and both gradients are the float64 model's on the same tensors, and so is the
     DeviceValueNorm's state."""
     import torch
-    import test_gpu_evaluate as tge
-    env = tge._env(layout)
-    pol, (ah, asd), _ = tge._heads(env, seed=1)
-    buf = tge._collect(env, pol, 6)
+    env = dp.env(layout)
+    pol, (ah, asd), _ = dp.heads(env, seed=1)
+    buf = dp.collect(env, pol, 6)
     vn = DeviceValueNorm(DEV)
     vn.load_state_dict({"running_mean": torch.tensor([0.1]), "running_mean_sq": torch.tensor([0.75]),
                         "debiasing_term": torch.tensor(0.5)})

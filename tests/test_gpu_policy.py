@@ -6,11 +6,11 @@ every output; then the public surface and three closed collect steps on a 4-env,
 import numpy as np
 import pytest
 
-import gnn_model as gm
+import device_policy_cases as dp
 import policy_abi as pa
 import policy_cases as pc
 import policy_model as pm
-from lsm import capi, gnn, policy
+from lsm import capi, policy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -92,27 +92,6 @@ def test_device_matches_host(lib, which):
             np.testing.assert_array_equal(dev[mode]["actions_i32"][dec], host[mode]["actions_i32"][dec])
 
 
-def _heads(env, recurrent_N=1, seed=0):
-    """(DevicePolicy, the four configs and state dicts) for env: the reference's default sizes."""
-    N, OBS, F = env.N, env.OBS, env.F
-    acfg, ccfg = gnn.GnnConfig(F=F, aggr="node"), gnn.GnnConfig(F=F, aggr="global_mean")
-    ah = policy.HeadConfig(kind="actor", in0=OBS, in1=16, num_actions=25, recurrent_N=recurrent_N)
-    ch = policy.HeadConfig(kind="critic", in0=N * OBS, in1=16, recurrent_N=recurrent_N)
-    asd, csd = pm.random_head_weights(ah, 11 + seed), pm.random_head_weights(ch, 12 + seed)
-    pol = policy.DevicePolicy(gnn.GraphEncoder(acfg, gm.default_weights(acfg, 5)[1], DEV),
-                              policy.PolicyHead(ah, policy.pack_head_weights(asd, ah), DEV),
-                              gnn.GraphEncoder(ccfg, gm.default_weights(ccfg, 6)[1], DEV),
-                              policy.PolicyHead(ch, policy.pack_head_weights(csd, ch), DEV))
-    return pol, (ah, asd), (ch, csd)
-
-
-def _env(layout="reference"):
-    from lsm.config import EnvArgs
-    from lsm.vec_env import GpuGraphVecEnv
-    return GpuGraphVecEnv(EnvArgs(num_agents=3, seed=1), num_envs=4, device=DEV, return_numpy=False, build_infos=False,
-                          adj_layout=layout)
-
-
 def _check_head(cfg, sd, inp, got, what):
     """One head's device outputs (torch tensors) against the float64 model fed the same inputs. The
     actions follow tests/policy_cases.py's rule (exact on decidable rows, adjacent or tied otherwise).
@@ -151,10 +130,10 @@ def test_public_surface(lib):
     env's own tensors), sampled and deterministic; load() changes the output; non-CUDA tensors, a 'node'
     critic and mismatched widths are refused; check=True raises on a bad uniform and clears the word."""
     import torch
-    env = _env()
+    env = dp.env()
     env.reset(0)
     env.step(torch.full((4, 3), 7, dtype=torch.int32, device=DEV), 0)
-    pol, (ah, asd), (ch, csd) = _heads(env)
+    pol, (ah, asd), (ch, csd) = dp.heads(env)
     n, N, M = 4, 3, 12
     rng = np.random.default_rng(3)
     st = torch.as_tensor((0.5 * rng.normal(size=(M, 1, 64))).astype(np.float32), device=DEV)
@@ -229,8 +208,8 @@ def test_closed_loop_with_the_replay_buffer(lib, layout):
     fed the same encoder output, row t's obs / share_obs, states and masks, and the same uniforms."""
     import torch
     from lsm.buffer import DeviceGraphBuffer
-    env = _env(layout)
-    pol, (ah, asd), (ch, csd) = _heads(env, seed=1)
+    env = dp.env(layout)
+    pol, (ah, asd), (ch, csd) = dp.heads(env, seed=1)
     n, N, M = 4, 3, 12
     buf = DeviceGraphBuffer(env, episode_length=4, policy_rows=dict(hidden_size=64, recurrent_N=1, act_dim=1,
                                                                     num_actions=None))
