@@ -42,6 +42,8 @@ UNITS = {
     "lsm_evaluate.hip": ["../../include/lsm_evaluate.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
     # the PPO loss and its gradient at the heads' outputs (include/lsm_loss.h, likewise outside build_id())
     "lsm_loss.hip": ["../../include/lsm_loss.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
+    # the heads' backward pass (include/lsm_backward.h, likewise outside build_id())
+    "lsm_backward.hip": ["../../include/lsm_backward.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
 ``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
-``include/lsm_policy.h``, ``include/lsm_evaluate.h`` and ``include/lsm_loss.h`` (``liblsm_rollout.so``).
+``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h`` and ``include/lsm_backward.h``
+(``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -68,6 +69,9 @@ EXPORTED_EVALUATE = ("lsm_head_evaluate_scratch_bytes", "lsm_head_evaluate", "ls
 # Every symbol include/lsm_loss.h declares (checked by tests/test_loss_capi.py).
 EXPORTED_LOSS = ("lsm_ppo_loss_scratch_bytes", "lsm_ppo_loss", "lsm_host_ppo_loss", "lsm_loss_last_error")
 LSM_LOSS_GROUP = 256
+# Every symbol include/lsm_backward.h declares (checked by tests/test_heads_backward_capi.py).
+EXPORTED_BACKWARD = ("lsm_head_backward_workspace_bytes", "lsm_head_backward", "lsm_host_head_backward")
+LSM_BWD_SLAB = 2048
 
 
 class LsmConfig(C.Structure):
@@ -176,6 +180,12 @@ class LsmLossIo(C.Structure):
                                           "dlogits", "dvalues", "imp_weights", "stats", "scratch", "bad")]
 
 
+class LsmBwdIo(C.Structure):
+    """lsm_bwd_io (include/lsm_backward.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("x0", "x1", "rnn_states", "masks", "available_actions", "dlogits",
+                                          "dvalues", "dweights", "dx0", "dx1", "workspace")]
+
+
 class LsmError(RuntimeError):
     pass
 
@@ -271,6 +281,10 @@ def load_library(path: str = LIB_PATH):
         "lsm_ppo_loss": (I32, [LsmLossConfig, C.POINTER(LsmLossIo), I64, P]),
         "lsm_host_ppo_loss": (I32, [LsmLossConfig, C.POINTER(LsmLossIo), I64]),
         "lsm_loss_last_error": (C.c_char_p, []),
+        # include/lsm_backward.h
+        "lsm_head_backward_workspace_bytes": (SZ, [LsmHeadConfig, I64, I32]),
+        "lsm_head_backward": (I32, [LsmHeadConfig, P, C.POINTER(LsmBwdIo), I64, I32, P]),
+        "lsm_host_head_backward": (I32, [LsmHeadConfig, P, C.POINTER(LsmBwdIo), I64, I32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -7,7 +7,8 @@ update and normalisation of the returns, the active-mask weighting -- in four la
 ``torch.autograd.backward([logits, values], [dlogits, dvalues])`` for a learner that keeps torch modules for
 the backward pass. ``DeviceValueNorm`` keeps ``ValueNorm``'s running statistics on the device, where the loss
 updates them, and hands ``DeviceGraphBuffer.compute_returns`` / ``.advantages`` the pair they take without an
-upload. No backward pass through the heads, no gradient clipping and no optimiser; float32 throughout (the
+upload. The heads' backward pass from these seeds is ``lsm.policy.PolicyHead.backward`` /
+``DevicePolicy.heads_backward``. No gradient clipping and no optimiser; float32 throughout (the
 reference's autocast and GradScaler are not imitated); PopArt is refused; no CPU fallback.
 """
 from __future__ import annotations

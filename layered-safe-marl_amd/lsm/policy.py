@@ -13,8 +13,11 @@ evaluation loop). ``PolicyHead.evaluate`` and ``DevicePolicy.evaluate_actions`` 
 (``csrc/lsm_evaluate.hip`` through ``include/lsm_evaluate.h``): on a minibatch of ``recurrent_generator`` or
 ``feed_forward_generator`` the GRU state is carried through each chunk's steps, and the log-probability of
 the stored action, the entropy and the values come back. ``DevicePolicy.ppo_loss`` adds the PPO loss and its
-gradient at the logits and the values (``lsm.loss``). No backward pass through the networks, Discrete action
-spaces only, and no CPU fallback, as elsewhere in the project.
+gradient at the logits and the values (``lsm.loss``). ``PolicyHead.backward`` and
+``DevicePolicy.heads_backward`` carry those two gradients back through the heads (``csrc/lsm_backward.hip``
+through ``include/lsm_backward.h``): the gradient of every packed head weight (``PolicyHead.gradients``) and
+the gradient at the encoder's output. No backward pass through the encoders, Discrete action spaces only, and
+no CPU fallback, as elsewhere in the project.
 
 Sampling is ``Categorical.sample`` as a distribution -- the inverse CDF of ``torch.rand`` uniforms -- not
 torch's generator stream: the same seed does not reproduce ``torch.multinomial``'s actions.
@@ -142,6 +145,9 @@ class PolicyHead(DeviceOp):
         self._struct = cfg.struct()
         self._out = OutputCache()
         self._eval_out = OutputCache()
+        self._bwd_out = OutputCache()
+        self._bwd_ws = {}   # stream -> the backward's workspace
+        self._last_dweights = None
         self._alloc_weights(head_weights_floats(cfg), weights)
 
     def load(self, state_dict, prefix: str = ""):
@@ -281,6 +287,82 @@ class PolicyHead(DeviceOp):
                      "a stored action that is not an integer in [0, num_actions) reached evaluate")
         return dict(out, logits=out["_logits"]) if keep_logits else out
 
+    def _bwd_outputs(self, Cn, T):
+        torch = _torch()
+        cfg, dev, f32, R = self.cfg, self.device, torch.float32, Cn * T
+        return {"dweights": torch.empty((self._n,), dtype=f32, device=dev),
+                "dx0": torch.empty((R, cfg.in0), dtype=f32, device=dev) if cfg.in0 else None,
+                "dx1": torch.empty((R, cfg.in1), dtype=f32, device=dev)}
+
+    def _bwd_workspace(self, Cn, T, sh):
+        """The stream's one workspace, grown to the largest need seen on it (never one per minibatch size: it
+        is 6.8 KB per row at the reference's defaults, 3.5 GB at 512000 rows)."""
+        nbytes = int(self.lib.lsm_head_backward_workspace_bytes(self._struct, Cn, T))
+        if nbytes == 0:
+            raise PolicyError(self.lib.lsm_policy_last_error().decode())
+        ws = self._bwd_ws.get(sh)
+        if ws is None or ws.numel() * 8 < nbytes:
+            self._bwd_ws.pop(sh, None)   # released first: the two need not be held together
+            ws = None
+            torch = _torch()
+            ws = self._bwd_ws[sh] = torch.empty((nbytes // 8,), dtype=torch.float64, device=self.device)
+        return ws
+
+    def backward(self, x0, x1, rnn_states, masks, T, dlogits=None, dvalues=None, available_actions=None,
+                 dx: bool = False):
+        """The backward pass (include/lsm_backward.h) on evaluate's minibatch: x0, x1, rnn_states, masks and T
+        as evaluate takes them, and the gradient at the head's output -- dlogits [T*C, num_actions] (actor;
+        entries under available_actions == 0 are read as 0) or dvalues [T*C, 1] or [T*C] (critic), as
+        lsm.loss.PPOLoss returns them. Four launches, no host synchronisation. Returns preallocated device
+        tensors, cached per (C, T, stream) and valid until the next call with them: dweights [floats of the
+        blob] -- the gradient of every packed weight in the blob's own layout, overwritten, not accumulated
+        (gradients() names its entries) -- and, with dx=True, dx0 [T*C, in0] (None when in0 == 0) and dx1
+        [T*C, in1], the gradient at the two input blocks; with dx=False they are not computed and come back
+        as None. The workspace (lsm_head_backward_workspace_bytes: about 6.8 KB per row at the reference's
+        defaults, 3.5 GB at 512000 rows) is held once per stream and grown to the largest call seen on it."""
+        cfg = self.cfg
+        T = 1 if T is None else int(T)
+        R, x0, x1, rnn_states, masks = self._inputs(x0, x1, rnn_states, masks, T, "[T*C, in1]", "PolicyHead.backward")
+        Cn = R // T
+        if cfg.kind == "actor":
+            if dlogits is None:
+                raise PolicyError("the actor's backward starts from dlogits")
+            dlogits = self._tensor(dlogits, "dlogits", R * cfg.num_actions)
+            if available_actions is not None:
+                available_actions = self._tensor(available_actions, "available_actions", R * cfg.num_actions)
+            dvalues = None
+        else:
+            if dvalues is None:
+                raise PolicyError("the critic's backward starts from dvalues")
+            dvalues = self._tensor(dvalues, "dvalues", R)
+            dlogits = available_actions = None
+        sh = self._stream()
+        out = self._bwd_out.get((Cn, T, sh), lambda: self._bwd_outputs(Cn, T))
+        ws = self._bwd_workspace(Cn, T, sh)
+        io = capi.LsmBwdIo(x0=ptr(x0), x1=ptr(x1), rnn_states=ptr(rnn_states), masks=ptr(masks),
+                           available_actions=ptr(available_actions), dlogits=ptr(dlogits), dvalues=ptr(dvalues),
+                           dweights=ptr(out["dweights"]), dx0=ptr(out["dx0"]) if dx else None,
+                           dx1=ptr(out["dx1"]) if dx else None, workspace=ptr(ws))
+        rc = self.lib.lsm_head_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), Cn, T,
+                                        C.c_void_p(sh))
+        self._finish(rc, self.lib.lsm_policy_last_error, False, "")
+        self._last_dweights = out["dweights"]
+        return {"dweights": out["dweights"], "dx0": out["dx0"] if dx else None, "dx1": out["dx1"] if dx else None}
+
+    def gradients(self, prefix: str = ""):
+        """{state-dict name: gradient}: views, without a copy, of the last backward()'s dweights in the
+        parameters' shapes, under the names of head_weight_entries (feature_norm entries only with it on).
+        They are that call's cached tensor: valid until the next backward() with its (C, T, stream)."""
+        if self._last_dweights is None:
+            raise PolicyError("gradients() follows a backward()")
+        out, o = {}, 0
+        for name, shape in head_weight_entries(self.cfg):
+            n = int(np.prod(shape))
+            if self.cfg.feature_norm or "base.feature_norm." not in name:
+                out[prefix + name] = self._last_dweights[o:o + n].view(shape)
+            o += n
+        return out
+
 
 class DevicePolicy:
     """GR_MAPPOPolicy's forward methods on the device. get_actions: the actor's and the critic's encoder and
@@ -307,6 +389,7 @@ class DevicePolicy:
         self.actor_encoder, self.actor_head = actor_encoder, actor_head
         self.critic_encoder, self.critic_head = critic_encoder, critic_head
         self.last_actor = self.last_critic = None   # the heads' own output dicts of the last call (features too)
+        self.last_head_inputs = None   # evaluate_actions' (x0, encoder output) per head, for heads_backward
 
     def get_actions(self, env, rnn_states, rnn_states_critic, masks, deterministic: bool = False, generator=None,
                     available_actions=None, buffer=None):
@@ -436,6 +519,7 @@ class DevicePolicy:
         c_feat = self.critic_encoder.forward(mb["node_obs"], mb["adj"], mb["agent_id"])
         c = self.critic_head.evaluate(cent, c_feat, mb.get("rnn_states_critic"), mb.get("masks"), T)
         self.last_actor, self.last_critic = a, c
+        self.last_head_inputs = {"actor": (obs, a_feat), "critic": (cent, c_feat)}   # what heads_backward needs
         out = {"values": c["values"], "action_log_probs": a["action_log_probs"], "dist_entropy": a["dist_entropy"],
                "entropy": a["entropy"]}
         if logits:
@@ -468,3 +552,33 @@ class DevicePolicy:
                            returns=first("returns"), active_masks=mb.get("active_masks"),
                            available_actions=mb.get("available_actions"), value_norm=value_norm, check=check)
         return dict(out, logits=ev["logits"], values=ev["values"], action_log_probs=ev["action_log_probs"])
+
+    def heads_backward(self, mb, loss_out, data_chunk_length=None, update_actor: bool = True, dx: bool = False):
+        """The heads' half of loss.backward() on the minibatch ppo_loss (or evaluate_actions) just ran on and
+        the dict ppo_loss returned: PolicyHead.backward of both heads from loss_out's dlogits and dvalues, on
+        the encoder outputs evaluate_actions kept (last_head_inputs; the encoders' next call overwrites them).
+        update_actor=False: the critic alone, as ppo_loss's flag. Two head calls, eight launches, no host
+        synchronisation. Returns {'actor': ..., 'critic': ...}, each PolicyHead.backward's dict ('actor' None
+        without update_actor); with dx=True their dx1 is the gradient at each encoder's output, the seed of
+        the encoder's backward. Every weight's gradient is then in actor_head.gradients() /
+        critic_head.gradients()."""
+        if self.last_head_inputs is None:
+            raise PolicyError("heads_backward follows ppo_loss or evaluate_actions on the same minibatch")
+        if self.actor_encoder is self.critic_encoder:
+            raise PolicyError("heads_backward needs two encoder objects: a shared one's cached output holds the "
+                              "critic's features by now, and the actor would be differentiated at them")
+        T = None if data_chunk_length is None else int(data_chunk_length)
+        out = {"actor": None}
+        if update_actor:
+            if loss_out.get("dlogits") is None:
+                raise PolicyError("loss_out has no dlogits")
+            x0, x1 = self.last_head_inputs["actor"]
+            out["actor"] = self.actor_head.backward(x0, x1, mb.get("rnn_states"), mb.get("masks"), T,
+                                                    dlogits=loss_out["dlogits"],
+                                                    available_actions=mb.get("available_actions"), dx=dx)
+        if loss_out.get("dvalues") is None:
+            raise PolicyError("loss_out has no dvalues")
+        x0, x1 = self.last_head_inputs["critic"]
+        out["critic"] = self.critic_head.backward(x0, x1, mb.get("rnn_states_critic"), mb.get("masks"), T,
+                                                  dvalues=loss_out["dvalues"], dx=dx)
+        return out

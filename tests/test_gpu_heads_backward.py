@@ -1,0 +1,191 @@
+"""GPU tests of the heads' backward pass (csrc/lsm_backward.hip through include/lsm_backward.h and
+lsm/policy.py): the kernels against tests/heads_backward_model.py's float64 autograd within the tolerance
+measured per case and gradient tensor (4 * e32 + 4 * 2^-23 * s) on tests/heads_backward_cases.py's cases, with
+canaries around every output and the workspace, twice bit-equal; the kernels against the host entry point;
+then the public surface: PolicyHead.backward on a side stream, its cache, and a closed loop of collect,
+recurrent_generator, ppo_loss and heads_backward against the torch modules' autograd."""
+import numpy as np
+import pytest
+
+import device_policy_cases as dp
+import evaluate_cases as ec
+import heads_backward_cases as hc
+import heads_backward_model as hm
+import policy_model as pm
+from lsm import capi, policy
+from lsm.loss import DeviceValueNorm, LossConfig, PPOLoss
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from lsm import build
+    build.build(verbose=False)
+    return capi.load_library()
+
+
+@pytest.mark.parametrize("kind", ["actor", "critic"])
+@pytest.mark.parametrize("shape", hc.SHAPES, ids=lambda s: "C%d_T%d" % s)
+def test_shapes(lib, kind, shape):
+    hc.check(lib, hc.shape_case(kind, *shape), DEV)
+
+
+@pytest.mark.parametrize("name", sorted(ec.OPTIONS))
+def test_options(lib, name):
+    hc.check(lib, hc.option_case(name), DEV)
+
+
+@pytest.mark.parametrize("kind", ["actor", "critic"])
+def test_zero_masks(lib, kind):
+    hc.check(lib, hc.masks_case(kind), DEV)
+
+
+def test_available_actions(lib):
+    hc.avail_checks(lib, DEV)
+
+
+@pytest.mark.parametrize("kind", ["actor", "critic"])
+@pytest.mark.parametrize("rows", [hc.SLAB - 1, hc.SLAB, hc.SLAB + 1, 3 * hc.SLAB + 2])
+def test_slab_boundaries(lib, kind, rows):
+    hc.check(lib, hc.slab_case(kind, rows), DEV)
+
+
+def test_structure(lib):
+    hc.structure_checks(lib, DEV)
+
+
+def test_same_call_twice_and_null_outputs(lib):
+    hc.twice_and_null_checks(lib, DEV)
+
+
+def test_refusals_write_nothing_on_the_device(lib):
+    hc.refusal_checks(lib, DEV)
+
+
+@pytest.mark.parametrize("which", ["actor 65 10", "critic 129 2", "option recurrent_N 2",
+                                   "option critic recurrent_N 2 hidden48"])
+def test_device_matches_host(lib, which):
+    """The kernels and lsm_host_head_backward run one text per stage; exp / tanh / rsqrt and the FMA
+    contraction differ in the last place, so the two are compared with the case's bound, not for bit equality
+    (the host entry point against the model is tests/test_heads_backward_capi.py's). The cases are the
+    well-conditioned widths (64 and 48): one bound for the difference of two float32 evaluations presumes that a
+    last-place difference stays one, which rows whose LayerNorm gains multiply into the hundreds (hidden 5)
+    do not grant; the kernels at those widths are checked against the model in test_options."""
+    kind, rest = which.split(" ", 1)
+    case = hc.option_case(rest) if kind == "option" else hc.shape_case(kind, *map(int, rest.split()))
+    host = hc.run(lib, case.cfg, case.blob, case.inp, case.dout, case.C, case.T, None)
+    dev = hc.check(lib, case, DEV)
+    h = dict(hc.entries(case.cfg, host["dweights"]), **{k: host[k] for k in ("dx0", "dx1") if k in host})
+    d = dict(hc.entries(case.cfg, dev["dweights"]), **{k: dev[k] for k in ("dx0", "dx1") if k in dev})
+    for k, (tol, _) in case.tol.items():
+        err = float(np.abs(d[k].astype(np.float64) - h[k]).max())
+        print("backward device vs host %s %s: %.3e (tol %.3e)" % (which, k, err, tol))
+        assert err <= tol, (which, k, err, tol)
+
+
+# ---- the public surface ---------------------------------------------------------------------------------------
+
+def _head_and_inputs(case):
+    import torch
+    head = policy.PolicyHead(case.cfg, case.blob, DEV)
+    t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=DEV)
+    inp = case.inp
+    args = (t(inp["x0"]), t(inp["x1"]), t(inp["states"]), t(inp["masks"]), case.T)
+    seed = {"dlogits" if case.cfg.kind == "actor" else "dvalues": t(case.dout)}
+    return head, args, seed
+
+
+def test_policy_head_backward_on_a_side_stream_and_its_cache(lib):
+    """PolicyHead.backward on a side stream without a synchronisation in between: the model's gradients; the
+    same tensors come back for the same (C, T, stream), other ones for another stream; gradients() are views
+    of dweights."""
+    import torch
+    case = hc.shape_case("actor", 65, 10)
+    head, args, seed = _head_and_inputs(case)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(device=DEV)
+    with torch.cuda.stream(side):
+        out = head.backward(*args, dx=True, **seed)
+        again = head.backward(*args, dx=True, **seed)
+        grads = head.gradients()
+        got = {"dweights": out["dweights"].clone(), "dx0": out["dx0"].clone(), "dx1": out["dx1"].clone()}
+    side.synchronize()
+    for k in ("dweights", "dx0", "dx1"):
+        assert again[k] is out[k], k
+    hc.compare({k: v.cpu().numpy() for k, v in got.items()}, case, "backward PolicyHead side stream")
+    base = out["dweights"].data_ptr()
+    o = 0
+    for name, shape in policy.head_weight_entries(case.cfg):
+        assert grads[name].data_ptr() == base + 4 * o and tuple(grads[name].shape) == tuple(shape), name
+        o += int(np.prod(shape))
+    want = policy.unpack_head_weights(out["dweights"].cpu().numpy(), case.cfg)
+    for k, v in want.items():
+        np.testing.assert_array_equal(grads[k].cpu().numpy(), v)
+    main = head.backward(*args, dx=False, **seed)
+    assert main["dweights"] is not out["dweights"] and main["dx0"] is None and main["dx1"] is None
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(main["dweights"].cpu().numpy().view(np.int32), got["dweights"].cpu().numpy().view(np.int32))
+    # one workspace per stream, grown to the largest call: a smaller minibatch on the same stream reuses it
+    assert len(head._bwd_ws) == 2
+    held = {k: v.data_ptr() for k, v in head._bwd_ws.items()}
+    small = head.backward(args[0][:130], args[1][:130], args[2][:65], args[3][:130], 2, dlogits=seed["dlogits"][:130])
+    assert small["dweights"] is not main["dweights"]
+    assert {k: v.data_ptr() for k, v in head._bwd_ws.items()} == held
+    with pytest.raises(policy.PolicyError, match="dlogits"):
+        head.backward(*args)
+    with pytest.raises(policy.PolicyError, match="no CPU fallback"):
+        head.backward(args[0], args[1].cpu(), *args[2:], **seed)
+    with pytest.raises(policy.PolicyError, match="not chunks of T"):
+        head.backward(*args[:4], 7, **seed)
+
+
+@pytest.mark.parametrize("layout", ["reference", "compact"])
+def test_heads_backward_closes_the_loop_on_a_collected_minibatch(lib, layout):
+    """Six collect steps, one recurrent_generator minibatch with data_chunk_length 3, DevicePolicy.ppo_loss,
+    DevicePolicy.heads_backward: every head parameter's gradient and dx1 are within the criterion of the torch
+    modules' autograd on the downloaded minibatch (the same inputs, encoder outputs and seeds)."""
+    import torch
+    env = dp.env(layout)
+    pol, (ah, asd), (ch, csd) = dp.heads(env, seed=1)
+    buf = dp.collect(env, pol, 6)
+    vn = DeviceValueNorm(DEV)
+    next_value = pol.get_values(env, buf.rnn_states_critic[-1], buf.masks[-1], buffer=buf, row=-1)
+    buf.compute_returns(next_value, vn, gamma=0.99, gae_lambda=0.95)
+    adv, _ = buf.advantages(vn)
+    mb = next(iter(buf.recurrent_generator(adv, 1, 3)))
+    R = int(mb["obs"].shape[0])
+    loss = PPOLoss(LossConfig(num_actions=25), DEV)
+    out = pol.ppo_loss(mb, loss, vn, data_chunk_length=3)
+    g = pol.heads_backward(mb, out, data_chunk_length=3, dx=True)
+    np_ = lambda x: x.detach().cpu().numpy()
+    a_x0, a_x1 = pol.last_head_inputs["actor"]
+    c_x0, c_x1 = pol.last_head_inputs["critic"]
+    sides = (("actor", ah, asd, pol.actor_head, dict(x0=np_(a_x0), x1=np_(a_x1), states=np_(mb["rnn_states"]),
+                                                      masks=np_(mb["masks"]), avail=None), np_(out["dlogits"])),
+             ("critic", ch, csd, pol.critic_head, dict(x0=np_(c_x0), x1=np_(c_x1), states=np_(mb["rnn_states_critic"]),
+                                                        masks=np_(mb["masks"])), np_(out["dvalues"]).reshape(R)))
+    for who, cfg, sd, head, inp, seed in sides:
+        g64, g32 = hm.model64(cfg, sd, inp, seed, R // 3, 3), hm.model32(cfg, sd, inp, seed, R // 3, 3)
+        assert hc.same_side(g64["pre"], g32["pre"]), "a ReLU pre-activation of this minibatch is undecidable"
+        grads = {k: np_(v) for k, v in head.gradients().items()}
+        grads["dx1"] = np_(g[who]["dx1"])
+        grads["dx0"] = np_(g[who]["dx0"])
+        assert set(grads) == set(g64) - {"out", "pre"}
+        for k in sorted(grads):
+            tol, e32 = pm.tensor_bound(g64[k], g32[k])
+            assert np.abs(g64[k]).max() > 0, k
+            pm.assert_close(grads[k], g64[k], tol, e32, "backward closed loop %s %s %s" % (layout, who, k))
+    # the critic half alone leaves the actor's gradients alone and gives the critic's bytes again
+    first = pol.critic_head.gradients()["v_out.weight"].clone()
+    half = pol.heads_backward(mb, out, data_chunk_length=3, update_actor=False)
+    assert half["actor"] is None and half["critic"]["dx1"] is None
+    assert torch.equal(pol.critic_head.gradients()["v_out.weight"].view(torch.int32), first.view(torch.int32))
+    # a shared encoder object's cached output would hold the critic's features by now: refused, not differentiated
+    shared = policy.DevicePolicy(pol.critic_encoder, pol.actor_head, pol.critic_encoder, pol.critic_head)
+    shared.last_head_inputs = pol.last_head_inputs
+    with pytest.raises(policy.PolicyError, match="two encoder objects"):
+        shared.heads_backward(mb, out, data_chunk_length=3)
+    buf.detach()
+    env.close()
