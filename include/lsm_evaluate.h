@@ -48,8 +48,9 @@
  * bit-reproducible. A workgroup owns 64 chunks and keeps, per chunk, the input row, two activation rows and
  * recurrent_N state rows in LDS: 256 * (pad(max(in, Hd)) + 2 pad(max(Hd, A)) + recurrent_N pad(Hd)) bytes
  * with pad(w) = round_up(w, 4) + 4. A config that needs more than the 163840 bytes a workgroup has is
- * refused by both entry points (it takes hidden > 64 together with wide inputs; hidden 64 with
- * recurrent_N 1 fits at every input width).
+ * refused by both entry points (hidden 64 fits at every input width and recurrent_N; with recurrent_N 1
+ * hidden 128 fits up to in = 240; with recurrent_N 2 hidden 124 is the largest that fits (up to in = 124)
+ * and hidden 128 does not at any width, though lsm_head_forward takes it). lsm_head_plan (lsm_policy.h) answers for a config.
  *
  * Return value: 0 on success; nonzero on an argument error, before any launch or write, with the text in
  * lsm_policy_last_error() (prefix "evaluate: "). Refused: everything lsm_head_forward refuses for the config

@@ -108,6 +108,21 @@ int lsm_host_gnn_forward(lsm_gnn_config cfg, const float* weights, const float* 
 
 const char* lsm_gnn_last_error(void);
 
+/* The launch plan lsm_gnn_forward would use for these sizes (what lsm_kernel_name is for the step kernels):
+ * filled on the host by the launch's own code, nothing is launched and no pointer is needed. */
+typedef struct lsm_gnn_launch_plan {
+  int32_t TS;        /* lanes per graph: the power of two >= E, at least 32 */
+  int32_t G;         /* graphs per workgroup: 256 / TS, fewer when their LDS does not fit; G * TS threads */
+  int32_t adj_lds;   /* 1: the adjacency is staged in LDS */
+  int32_t fast;      /* 1: the <16, 16> instance, 0: the generic one */
+  int32_t SA, SK;    /* padded row strides (floats) of the activation and the k / v buffers */
+  int64_t lds_bytes; /* the workgroup's dynamic LDS */
+} lsm_gnn_launch_plan;
+
+/* masked != 0: the compact layout (masks != NULL). Returns 0, or nonzero with lsm_gnn_forward's refusal of
+ * these sizes in lsm_gnn_last_error() (the pointer checks are not made); *out is written on success only. */
+int lsm_gnn_plan(lsm_gnn_config cfg, int64_t B, int32_t E, int32_t N, int32_t masked, lsm_gnn_launch_plan* out);
+
 #ifdef __cplusplus
 }
 #endif

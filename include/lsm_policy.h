@@ -117,6 +117,36 @@ int lsm_host_head_forward(lsm_head_config cfg, const float* weights, const lsm_h
 
 const char* lsm_policy_last_error(void);
 
+/* The launch plan of the three head routines for a config and sizes (what lsm_kernel_name is for the step
+ * kernels): filled on the host by the launches' own code; nothing is launched and no pointer is needed.
+ * Strides are in floats per tile row (a tile is 64 rows or chunks), offsets in floats from the start of
+ * lsm_head_backward's workspace (include/lsm_backward.h); a field the routine does not have is 0. */
+enum { LSM_HEAD_PLAN_FORWARD = 0, LSM_HEAD_PLAN_EVALUATE = 1, LSM_HEAD_PLAN_BACKWARD = 2 };
+#define LSM_HEAD_PLAN_MAX_JOBS 17
+
+typedef struct lsm_head_plan_job {
+  int32_t nout, nin; /* the job's matrix [nout][nin] and its bias column (column nin) */
+  int32_t ti_n;      /* its 64-wide tiles along i (columns 0 .. nin); ceil(nout / 64) tiles along j */
+  int32_t tile0;     /* its first tile */
+} lsm_head_plan_job;
+
+typedef struct lsm_head_launch_plan {
+  int32_t SX, SA, SH;     /* the input row, an activation row, a GRU state row (forward: SH = 0, h lives in
+                             the input row; backward: stage 1's) */
+  int32_t S0, S1, S2, HP; /* backward, stage 2: rows B0, B1, B2 and the gate sections' width in B0 */
+  int32_t njobs, ntiles;  /* backward, stage 3 */
+  int64_t lds_bytes[2];   /* forward and evaluate: [0], the one launch; backward: stage 1, stage 2 */
+  int64_t slabs;          /* backward: ceil(T * C / LSM_BWD_SLAB) */
+  int64_t ws_floats;      /* backward: the workspace's documented size in floats */
+  int64_t o_feat;         /* backward: the saved features [T*C][hidden] */
+  int64_t o_ho[2];        /* backward: GRU layer k's saved h' [T*C][hidden] */
+  lsm_head_plan_job job[LSM_HEAD_PLAN_MAX_JOBS];
+} lsm_head_launch_plan;
+
+/* Returns 0, or nonzero with the routine's own refusal of the config and sizes in lsm_policy_last_error()
+ * (the pointer checks are not made; the forward takes C * T rows); *out is written on success only. */
+int lsm_head_plan(lsm_head_config cfg, int32_t which, int64_t C, int32_t T, lsm_head_launch_plan* out);
+
 #ifdef __cplusplus
 }
 #endif

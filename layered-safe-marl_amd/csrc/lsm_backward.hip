@@ -718,6 +718,26 @@ int make_bwd(const lsm_head_config& c, const float* weights, const lsm_bwd_io* i
 
 }  // namespace
 
+int lsm_backward_fill_plan(const lsm_head_config& c, int64_t C, int32_t T, lsm_head_launch_plan* out) {
+  Bwd n;
+  if (make_plan(c, C, T, &n)) return 1;
+  static_assert(MAX_JOBS == LSM_HEAD_PLAN_MAX_JOBS, "lsm_policy.h's job array holds every job");
+  out->SX = n.SX, out->SA = n.SA, out->SH = n.SH;
+  out->S0 = n.S0, out->S1 = n.S1, out->S2 = n.S2, out->HP = n.HP;
+  out->njobs = n.njobs, out->ntiles = n.ntiles;
+  out->lds_bytes[0] = (int64_t)((size_t)TILE * fwd_tile_floats(n) * sizeof(float));
+  out->lds_bytes[1] = (int64_t)((size_t)TILE * bwd_tile_floats(n) * sizeof(float));
+  out->slabs = n.slabs;
+  out->ws_floats = n.ws_floats;
+  out->o_feat = n.o_feat;
+  for (int k = 0; k < MAX_RNN; ++k) out->o_ho[k] = n.o_ho[k];
+  for (int q = 0; q < n.njobs; ++q) {
+    const Job& jb = n.job[q];
+    out->job[q].nout = jb.nout, out->job[q].nin = jb.nin, out->job[q].ti_n = jb.ti_n, out->job[q].tile0 = jb.tile0;
+  }
+  return 0;
+}
+
 extern "C" {
 
 size_t lsm_head_backward_workspace_bytes(lsm_head_config cfg, int64_t C, int32_t T) {

@@ -207,8 +207,8 @@ int64_t groups_of(int64_t C) { return (C + TILE - 1) / TILE; }
 
 size_t tile_floats(const Eval& n) { return (size_t)n.SX + 2 * (size_t)n.SA + (size_t)n.RN * n.SH; }
 
-// every check of one call, shared by the device and the host entry point; fills n; 0 when fine
-int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io* io, int64_t C, int32_t T, Eval* n) {
+// the config's part of a call: the blob's layout, the LDS strides and the tile's LDS need; 0 when fine
+int make_shape(const lsm_head_config& c, Eval* n) {
   if (layout(c, n, "evaluate: ") == 0) return 1;
   n->SH = pad(n->Hd);
   const size_t need = (size_t)TILE * tile_floats(*n) * sizeof(float);
@@ -220,11 +220,22 @@ int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io*
              need, n->SX, n->SA, n->RN, n->SH, WORKGROUP_LDS_BYTES);
     return fail(msg);
   }
-  if (!weights) return fail("weights is null");
-  if (!io) return fail("io is null");
+  return 0;
+}
+
+int check_sizes(int64_t C, int32_t T) {
   if (T < 1) return fail("T < 1");
   if (C < 0) return fail("C < 0");
   if (C > INT32_MAX / (int64_t)T) return fail("T * C exceeds INT32_MAX rows; split the minibatch");
+  return 0;
+}
+
+// every check of one call, shared by the device and the host entry point; fills n; 0 when fine
+int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io* io, int64_t C, int32_t T, Eval* n) {
+  if (make_shape(c, n)) return 1;
+  if (!weights) return fail("weights is null");
+  if (!io) return fail("io is null");
+  if (check_sizes(C, T)) return 1;
   // the fields this config does not read or write are dropped first: they are not checked either
   lsm_eval_io f = *io;
   if (n->in0 == 0) f.x0 = nullptr;
@@ -263,6 +274,14 @@ int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io*
 }
 
 }  // namespace
+
+int lsm_evaluate_fill_plan(const lsm_head_config& c, int64_t C, int32_t T, lsm_head_launch_plan* out) {
+  Eval n;
+  if (make_shape(c, &n) || check_sizes(C, T)) return 1;
+  out->SX = n.SX, out->SA = n.SA, out->SH = n.SH;
+  out->lds_bytes[0] = (int64_t)((size_t)TILE * tile_floats(n) * sizeof(float));
+  return 0;
+}
 
 extern "C" {
 

@@ -410,15 +410,18 @@ size_t layout(const lsm_gnn_config& c, Net* n) {
 // every check of one call, shared by the device and the host entry point; fills n; 0 when fine
 int make_net(const lsm_gnn_config& c, const float* weights, const float* node_obs, const float* adj,
              const uint64_t* masks, int64_t B, int32_t E, int32_t N, const int64_t* agent_id, float* out,
-             int64_t* bad, Net* n) {
+             int64_t* bad, Net* n, int plan_masked = -1) {
+  // lsm_gnn_plan: plan_masked >= 0 stands for masks != NULL, and the pointers are neither given nor checked
+  const bool plan = plan_masked >= 0;
+  const bool masked = plan ? plan_masked != 0 : masks != nullptr;
   if (layout(c, n) == 0) return 1;
-  if (!weights) return fail("weights is null");
+  if (!plan && !weights) return fail("weights is null");
   if (B < 0) return fail("B < 0");
   if (B > INT32_MAX) return fail("B exceeds INT32_MAX graphs; split the batch");
   if (E < 1 || E > 256) return fail("E must be in [1, 256]");
-  if (masks && (N < 1 || B % N != 0)) return fail("compact layout: B must be a multiple of N > 0");
-  if (B > 0 && (!node_obs || !adj || !out)) return fail("node_obs / adj / out is null");
-  if (c.aggr == LSM_GNN_NODE && !agent_id) return fail("node aggregation needs agent_id");
+  if (masked && (N < 1 || B % N != 0)) return fail("compact layout: B must be a multiple of N > 0");
+  if (!plan && B > 0 && (!node_obs || !adj || !out)) return fail("node_obs / adj / out is null");
+  if (!plan && c.aggr == LSM_GNN_NODE && !agent_id) return fail("node aggregation needs agent_id");
   if (((uintptr_t)weights & 3) || ((uintptr_t)node_obs & 3) || ((uintptr_t)adj & 3) || ((uintptr_t)out & 3) ||
       ((uintptr_t)masks & 7) || ((uintptr_t)agent_id & 7) || ((uintptr_t)bad & 7))
     return fail("misaligned pointer");
@@ -431,7 +434,7 @@ int make_net(const lsm_gnn_config& c, const float* weights, const float* node_ob
   n->bad = bad;
   n->B = B;
   n->E = E;
-  n->N = masks ? N : 1;
+  n->N = masked ? N : 1;
   n->W = (E + 63) / 64;
   n->SA = pad(n->Hd > n->D ? n->Hd : n->D);
   n->SK = pad(n->Hd > n->HC ? n->Hd : n->HC);
@@ -453,6 +456,9 @@ int make_net(const lsm_gnn_config& c, const float* weights, const float* node_ob
 
 bool fast(const Net& n) { return n.Hd == 16 && n.C == 16; }
 
+// the workgroup's dynamic LDS
+size_t lds_bytes(const Net& n) { return (size_t)n.G * n.per_graph * sizeof(float); }
+
 }  // namespace
 
 extern "C" {
@@ -464,13 +470,27 @@ size_t lsm_gnn_weights_floats(lsm_gnn_config cfg) {
   return layout(cfg, &n);
 }
 
+int lsm_gnn_plan(lsm_gnn_config cfg, int64_t B, int32_t E, int32_t N, int32_t masked, lsm_gnn_launch_plan* out) {
+  Net n;
+  if (!out) return fail("plan: out is null");
+  if (make_net(cfg, nullptr, nullptr, nullptr, nullptr, B, E, N, nullptr, nullptr, nullptr, &n, masked != 0)) return 1;
+  out->TS = n.TS;
+  out->G = n.G;
+  out->adj_lds = n.adj_lds;
+  out->fast = fast(n);
+  out->SA = n.SA;
+  out->SK = n.SK;
+  out->lds_bytes = (int64_t)lds_bytes(n);
+  return 0;
+}
+
 int lsm_gnn_forward(lsm_gnn_config cfg, const float* weights, const float* node_obs, const float* adj,
                     const uint64_t* masks, int64_t B, int32_t E, int32_t N, const int64_t* agent_id, float* out,
                     int64_t* bad, void* hip_stream) {
   Net n;
   if (make_net(cfg, weights, node_obs, adj, masks, B, E, N, agent_id, out, bad, &n)) return 1;
   if (B == 0) return 0;
-  const size_t lds = (size_t)n.G * n.per_graph * sizeof(float);
+  const size_t lds = lds_bytes(n);
   const dim3 grid((unsigned)((B + n.G - 1) / n.G)), block((unsigned)(n.G * n.TS));
   auto kernel = fast(n) ? gnn_kernel<16, 16> : gnn_kernel<0, 0>;
   if (lds > 48 * 1024 &&

@@ -22,6 +22,12 @@
 // the text of lsm_policy_last_error() (thread-local, lsm_policy.hip): "<prefix><msg>"
 __attribute__((visibility("hidden"))) void lsm_policy_set_error(const char* prefix, const char* msg);
 
+// lsm_head_plan's parts that lsm_evaluate.hip and lsm_backward.hip fill from their own launch code
+__attribute__((visibility("hidden"))) int lsm_evaluate_fill_plan(const lsm_head_config& c, int64_t C, int32_t T,
+                                                                 lsm_head_launch_plan* out);
+__attribute__((visibility("hidden"))) int lsm_backward_fill_plan(const lsm_head_config& c, int64_t C, int32_t T,
+                                                                 lsm_head_launch_plan* out);
+
 namespace lsm_head_tile {
 
 #define LSM_HD __host__ __device__ __forceinline__

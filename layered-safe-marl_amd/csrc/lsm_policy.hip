@@ -169,13 +169,21 @@ int fail(const char* msg) {
 constexpr int MAX_TILE_BYTES = TILE * (pad(MAX_IN) + 2 * pad(MAX_HIDDEN)) * (int)sizeof(float);
 static_assert(MAX_TILE_BYTES <= WORKGROUP_LDS_BYTES, "the worst-case tile must fit one workgroup's LDS");
 
+int check_rows(int64_t M) {
+  if (M < 0) return fail("M < 0");
+  if (M > INT32_MAX) return fail("M exceeds INT32_MAX rows; split the batch");
+  return 0;
+}
+
+// the tile's LDS floats per row: the input row and two activation rows
+size_t tile_floats(const Shape& n) { return (size_t)n.SX + 2 * (size_t)n.SA; }
+
 // every check of one call, shared by the device and the host entry point; fills n; 0 when fine
 int make_head(const lsm_head_config& c, const float* weights, const lsm_head_io* io, int64_t M, Head* n) {
   if (layout(c, n, "head: ") == 0) return 1;
   if (!weights) return fail("weights is null");
   if (!io) return fail("io is null");
-  if (M < 0) return fail("M < 0");
-  if (M > INT32_MAX) return fail("M exceeds INT32_MAX rows; split the batch");
+  if (check_rows(M)) return 1;
   // the fields this config does not read or write are dropped first: they are not checked either
   lsm_head_io f = *io;
   if (n->in0 == 0) f.x0 = nullptr;
@@ -222,11 +230,34 @@ size_t lsm_head_weights_floats(lsm_head_config cfg) {
   return layout(cfg, &n, "head: ");
 }
 
+int lsm_head_plan(lsm_head_config cfg, int32_t which, int64_t C, int32_t T, lsm_head_launch_plan* out) {
+  if (!out) return lsm_policy_set_error("plan: ", "out is null"), 1;
+  lsm_head_launch_plan p = {};
+  if (which == LSM_HEAD_PLAN_FORWARD) {
+    Shape n;
+    if (layout(cfg, &n, "head: ") == 0) return 1;
+    if (T < 1) return fail("T < 1");
+    if (C < 0 || C > INT32_MAX / (int64_t)T) return check_rows(C < 0 ? C : (int64_t)INT32_MAX + 1);
+    const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
+    if (lds > (size_t)MAX_TILE_BYTES) return fail("the tile exceeds the LDS of one workgroup");
+    p.SX = n.SX, p.SA = n.SA;
+    p.lds_bytes[0] = (int64_t)lds;
+  } else if (which == LSM_HEAD_PLAN_EVALUATE) {
+    if (lsm_evaluate_fill_plan(cfg, C, T, &p)) return 1;
+  } else if (which == LSM_HEAD_PLAN_BACKWARD) {
+    if (lsm_backward_fill_plan(cfg, C, T, &p)) return 1;
+  } else {
+    return lsm_policy_set_error("plan: ", "unknown routine"), 1;
+  }
+  *out = p;
+  return 0;
+}
+
 int lsm_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_io* io, int64_t M, void* hip_stream) {
   Head n;
   if (make_head(cfg, weights, io, M, &n)) return 1;
   if (M == 0) return 0;
-  const size_t lds = (size_t)TILE * (n.SX + 2 * n.SA) * sizeof(float);
+  const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
   if (lds > (size_t)MAX_TILE_BYTES) return fail("the tile exceeds the LDS of one workgroup");
   const dim3 grid((unsigned)((M + TILE - 1) / TILE)), block(BLOCK);
   static std::atomic<bool> raised[MAX_DEVICES];   // to the limits' worst case
@@ -238,7 +269,7 @@ int lsm_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_i
 int lsm_host_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_io* io, int64_t M) {
   Head n;
   if (make_head(cfg, weights, io, M, &n)) return 1;
-  std::vector<float4> scratch((size_t)(n.SX + 2 * n.SA) / 4 + 1);
+  std::vector<float4> scratch(tile_floats(n) / 4 + 1);
   for (int64_t m = 0; m < M; ++m) tile_forward(n, n.w, m, 1, 0, 0, 1, 1, reinterpret_cast<float*>(scratch.data()));
   return 0;
 }

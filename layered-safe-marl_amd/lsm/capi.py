@@ -59,11 +59,15 @@ EXPORTED_MB_EDGES = ("lsm_mb_edges_workspace_bytes", "lsm_mb_edges_count", "lsm_
                      "lsm_mb_edges_last_error")
 LSM_MB_INDICES, LSM_MB_CHUNKS = 0, 1
 # Every symbol include/lsm_gnn.h declares (checked by tests/test_gnn_capi.py).
-EXPORTED_GNN = ("lsm_gnn_weights_floats", "lsm_gnn_forward", "lsm_host_gnn_forward", "lsm_gnn_last_error")
+EXPORTED_GNN = ("lsm_gnn_weights_floats", "lsm_gnn_forward", "lsm_host_gnn_forward", "lsm_gnn_last_error",
+                "lsm_gnn_plan")
 LSM_GNN_NODE, LSM_GNN_GLOBAL_MEAN, LSM_GNN_GLOBAL_MAX, LSM_GNN_GLOBAL_ADD = 0, 1, 2, 3
 # Every symbol include/lsm_policy.h declares (checked by tests/test_policy_capi.py).
-EXPORTED_POLICY = ("lsm_head_weights_floats", "lsm_head_forward", "lsm_host_head_forward", "lsm_policy_last_error")
+EXPORTED_POLICY = ("lsm_head_weights_floats", "lsm_head_forward", "lsm_host_head_forward", "lsm_policy_last_error",
+                   "lsm_head_plan")
 LSM_HEAD_ACTOR, LSM_HEAD_CRITIC = 0, 1
+LSM_HEAD_PLAN_FORWARD, LSM_HEAD_PLAN_EVALUATE, LSM_HEAD_PLAN_BACKWARD = 0, 1, 2
+LSM_HEAD_PLAN_MAX_JOBS = 17
 # Every symbol include/lsm_evaluate.h declares (checked by tests/test_evaluate_capi.py).
 EXPORTED_EVALUATE = ("lsm_head_evaluate_scratch_bytes", "lsm_head_evaluate", "lsm_host_head_evaluate")
 # Every symbol include/lsm_loss.h declares (checked by tests/test_loss_capi.py).
@@ -143,6 +147,23 @@ class LsmGnnConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("F", "num_embeddings", "embedding_size", "embed_hidden", "embed_layer_N",
                                          "embed_relu", "layer_norm", "C", "H", "concat", "layer_N", "relu", "aggr",
                                          "ego_only")]
+
+
+class LsmGnnLaunchPlan(C.Structure):
+    """lsm_gnn_launch_plan (include/lsm_gnn.h): what lsm_gnn_plan fills."""
+    _fields_ = [(n, C.c_int32) for n in ("TS", "G", "adj_lds", "fast", "SA", "SK")] + [("lds_bytes", C.c_int64)]
+
+
+class LsmHeadPlanJob(C.Structure):
+    """lsm_head_plan_job (include/lsm_policy.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("nout", "nin", "ti_n", "tile0")]
+
+
+class LsmHeadLaunchPlan(C.Structure):
+    """lsm_head_launch_plan (include/lsm_policy.h): what lsm_head_plan fills."""
+    _fields_ = ([(n, C.c_int32) for n in ("SX", "SA", "SH", "S0", "S1", "S2", "HP", "njobs", "ntiles")] +
+                [("lds_bytes", C.c_int64 * 2), ("slabs", C.c_int64), ("ws_floats", C.c_int64), ("o_feat", C.c_int64),
+                 ("o_ho", C.c_int64 * 2), ("job", LsmHeadPlanJob * LSM_HEAD_PLAN_MAX_JOBS)])
 
 
 class LsmHeadConfig(C.Structure):
@@ -267,11 +288,13 @@ def load_library(path: str = LIB_PATH):
         "lsm_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P, P]),
         "lsm_host_gnn_forward": (I32, [LsmGnnConfig, P, P, P, P, I64, I32, I32, P, P, P]),
         "lsm_gnn_last_error": (C.c_char_p, []),
+        "lsm_gnn_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnLaunchPlan)]),
         # include/lsm_policy.h
         "lsm_head_weights_floats": (SZ, [LsmHeadConfig]),
         "lsm_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64, P]),
         "lsm_host_head_forward": (I32, [LsmHeadConfig, P, C.POINTER(LsmHeadIo), I64]),
         "lsm_policy_last_error": (C.c_char_p, []),
+        "lsm_head_plan": (I32, [LsmHeadConfig, I32, I64, I32, C.POINTER(LsmHeadLaunchPlan)]),
         # include/lsm_evaluate.h
         "lsm_head_evaluate_scratch_bytes": (SZ, [I64, I32]),
         "lsm_head_evaluate": (I32, [LsmHeadConfig, P, C.POINTER(LsmEvalIo), I64, I32, P]),

@@ -30,6 +30,7 @@ import functools
 import numpy as np
 
 import evaluate_model as em
+import launch_plans as lp
 import policy_abi as pa
 import policy_cases as pc
 import policy_model as pm
@@ -197,6 +198,92 @@ def option_case(name):
     base, over = OPTIONS[name]
     return admitted("option " + name, dataclasses.replace(base, **over), OPTION_C, OPTION_T,
                     1 + sorted(OPTIONS).index(name))
+
+
+# ---- one case per launch plan and size limit (lsm_head_plan, include/lsm_policy.h) ---------------------------
+# Run by the evaluate and the backward tests alike (heads_backward_cases.plan_case), at C = 65; T = 3, or 2 for
+# the cases at a limit. "max" is resolved per routine by walking the library's own plan call
+# (tests/launch_plans.py): the evaluate takes every in <= 256 at hidden 64 and hidden 128 / 124 with
+# recurrent_N 1 / 2 (so the forward's `hidden128 recurrent_N 2` is refused here, see
+# test_launch_plans.py); the backward's limits are include/lsm_backward.h's 240, 172, 88, 76 and 248.
+# tests/test_launch_plans.py asserts that these cases' plans cover every branch of the backward's plan.
+PLAN_OPTIONS = {
+    "hidden128 rn0 in22": (ACTOR, dict(hidden=128, recurrent_N=0)),
+    "hidden128 rn0 max in": (ACTOR, dict(hidden=128, recurrent_N=0, width="max")),
+    "hidden64 rn1 max in": (ACTOR, dict(width="max")),
+    "critic hidden64 rn2 max in": (CRITIC, dict(recurrent_N=2, width="max")),
+    "rn1 max hidden": (CRITIC, dict(in0=6, hidden="max")),
+    "rn2 max hidden": (ACTOR, dict(recurrent_N=2, hidden="max")),
+    "layer_N 3": (ACTOR, dict(layer_N=3)),
+    "critic layer_N 4": (CRITIC, dict(layer_N=4)),
+    "hidden63": (ACTOR, dict(hidden=63)),
+    "hidden65": (ACTOR, dict(hidden=65)),
+    "critic hidden65 rn2": (CRITIC, dict(hidden=65, recurrent_N=2)),
+    "in63": (ACTOR, dict(width=63)),
+    "in65": (CRITIC, dict(width=65)),
+    "in127": (ACTOR, dict(width=127)),
+    "in128": (CRITIC, dict(width=128)),
+    "in129": (ACTOR, dict(width=129)),
+    "A64 hidden48": (ACTOR, dict(num_actions=64, hidden=48)),       # A > max(in, hidden)
+    # in0 + in1 = 1: eval_tile parks the dist_entropy partials in the input rows. Without the feature norm;
+    # with it LayerNorm(1) returns beta whatever the input (x - mean is 0), which the admission rule takes
+    # (no amplification: the gain is 0) but which tests nothing of the input path, so it is one case only.
+    "in1": (ACTOR, dict(in0=0, in1=1, feature_norm=False)),
+    "in1 x1 null": (ACTOR, dict(in0=1, in1=0, feature_norm=False)),
+    "in1 feature norm": (ACTOR, dict(in0=0, in1=1)),
+}
+# the forward's `hidden128 recurrent_N 2` is refused by the evaluate at every width (168960 bytes at in = 22);
+# what it does take of hidden 128 with an RNN is recurrent_N 1 up to in = 240, a tile of the whole LDS, which
+# the backward refuses at every width
+EVALUATE_ONLY = {"hidden128 rn1 max in": (ACTOR, dict(hidden=128, width="max"))}
+PLAN_OPTIONS.update(EVALUATE_ONLY)
+BACKWARD_PLAN_NAMES = tuple(n for n in sorted(PLAN_OPTIONS) if n not in EVALUATE_ONLY)
+PLAN_LIMITS = tuple(n for n in sorted(PLAN_OPTIONS) if "max" in PLAN_OPTIONS[n][1].values())
+
+
+def plan_cfg(name, which="evaluate"):
+    """The case's config for the routine `which` ('evaluate' or 'backward'): a 'max' is that routine's."""
+    base, over = PLAN_OPTIONS[name]
+    over = dict(over)
+    width, hidden = over.pop("width", None), over.pop("hidden", None)
+    cfg = dataclasses.replace(base, **over)
+    if hidden == "max":
+        cfg = dataclasses.replace(cfg, hidden=lp.largest_hidden(cfg, which))
+    elif hidden is not None:
+        cfg = dataclasses.replace(cfg, hidden=hidden)
+    if width == "max":
+        cfg = lp.with_in(cfg, lp.largest_in(cfg, which))
+    elif width is not None:
+        cfg = lp.with_in(cfg, width)
+    return cfg
+
+
+def plan_T(name):
+    return 2 if name in PLAN_LIMITS else OPTION_T
+
+
+def beyond(name, which="evaluate"):
+    """The limit case's config one step past its limit (None where the ABI's own limit, 256 or 128, is it)."""
+    cfg = plan_cfg(name, which)
+    if PLAN_OPTIONS[name][1].get("hidden") == "max":
+        return dataclasses.replace(cfg, hidden=cfg.hidden + 1) if cfg.hidden < 128 else None
+    return lp.with_in(cfg, cfg.in0 + cfg.in1 + 1) if cfg.in0 + cfg.in1 < 256 else None
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case(name):
+    return admitted("plan " + name, plan_cfg(name), OPTION_C, plan_T(name), 30 + sorted(PLAN_OPTIONS).index(name))
+
+
+def plan_checks(lib, name, device):
+    """The case against the model; a case at an LDS limit also shows the next size refused, nothing written."""
+    case = plan_case(name)
+    check(lib, case, device)
+    past = beyond(name) if name in PLAN_LIMITS else None
+    if past is not None:
+        small = em.random_inputs(past, 1, 1, 0)
+        run(lib, past, np.zeros(400000, np.float32), small, 1, 1, device, expect_rc=1)
+        assert "bytes of LDS" in lib.lsm_policy_last_error().decode()
 
 
 @functools.lru_cache(maxsize=None)

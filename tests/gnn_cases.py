@@ -8,6 +8,7 @@ import numpy as np
 
 import gnn_abi as ga
 import gnn_model as gm
+import launch_plans as lp
 from lsm.gnn import GnnConfig
 
 DEFAULT = GnnConfig(F=11)          # the reference's defaults (onpolicy/config.py:400-446)
@@ -107,6 +108,79 @@ def option_case(name):
     x, table, bits = gm.random_graphs(5, 24, cfg.F, seed=1 + sorted(OPTIONS).index(name), N=5)
     return Case("option " + name, cfg, x, ego_ids(5, 24), aggrs=OPTION_AGGRS.get(name, BOTH), compact=(table, bits, 5),
                 seed=2)
+
+
+# ---- one case per launch plan (lsm_gnn_plan, include/lsm_gnn.h) ---------------------------------------------
+# The sizes are read from the plan the library computes (tests/launch_plans.py), not restated here: "last" is
+# the last E whose adjacency is staged in LDS, "first" the one after it, "max" the largest accepted E.
+# tests/test_launch_plans.py asserts that these cases' plans cover every branch of the plan.
+GENERIC = dict(C=12, embed_hidden=20)
+WIDE = dict(F=64, H=4, C=64, concat=True, embed_hidden=64, embed_layer_N=4, layer_N=4)
+PLAN_CASES = {
+    "default E33": ({}, 33),                  # TS 64, four graphs per workgroup
+    "default E48": ({}, 48),                  # BASELINE config 4's graph
+    "default E64": ({}, 64),                  # G cut to 3 by the LDS: a 192-thread workgroup
+    "default E99": ({}, 99),                  # G cut to 1
+    "default E128": ({}, 128),                # the exact team size
+    "default adj_lds last": ({}, "last"),
+    "default adj_lds first": ({}, "first"),
+    "default E256": ({}, 256),
+    "generic E64": (GENERIC, 64),             # the generic instance with G cut (to 3)
+    "generic E65": (GENERIC, 65),
+    "generic E192": (GENERIC, 192),           # TS 256 without the adjacency in LDS
+    "generic adj_lds last": (GENERIC, "last"),
+    "generic adj_lds first": (GENERIC, "first"),
+    "wide corner max E": (WIDE, "max"),
+    # H 4, C 64 without concat: k and v rows of 260 floats; E = 65 does not fit (the largest E that does is
+    # found from the plan and is 62), so the case runs at the largest accepted E and 65 is asserted refused
+    "H4 C64 max E": (dict(H=4, C=64), "max"),
+}
+PLAN_SEED = 20
+
+
+def plan_cfg(name):
+    return dataclasses.replace(DEFAULT, **PLAN_CASES[name][0])
+
+
+def plan_E(name):
+    cfg, E = plan_cfg(name), PLAN_CASES[name][1]
+    if E == "max":
+        return lp.largest_E(cfg)
+    if E in ("last", "first"):
+        return lp.adj_switch(cfg)[E == "first"]
+    return E
+
+
+def plan_B(name):
+    """5, or G + 1 when a packed workgroup takes 5 or more, or 2 at the largest graphs: the smallest batch
+    with a partly filled last workgroup."""
+    cfg, E = plan_cfg(name), plan_E(name)
+    if E == 256:
+        return 2
+    G = lp.gnn_plan(cfg, 5, E)[0]["G"]
+    return 5 if G < 5 else G + 1
+
+
+def plan_of(name):
+    return lp.gnn_plan(plan_cfg(name), plan_B(name), plan_E(name))[0]
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case(name):
+    cfg, E, B = plan_cfg(name), plan_E(name), plan_B(name)
+    seed = PLAN_SEED + sorted(PLAN_CASES).index(name)
+    x, table, bits = gm.random_graphs(B, E, cfg.F, seed=seed, density=0.1 if E > 100 else 0.4, N=B)
+    return Case("plan " + name, cfg, x, ego_ids(B, E), compact=(table, bits, B), seed=seed)
+
+
+def refused_beyond(lib, name, device=None):
+    """The case's config one node beyond its largest accepted E: refused with the LDS text, nothing written."""
+    case = plan_case(name)
+    E = case.x.shape[1] + 1
+    x, table, bits = gm.random_graphs(1, E, case.cfg.F, seed=1)
+    src = ga.sources(table, bits, 1, device)["reference"]
+    ga.run(lib, case.cfg, case.weights()[1], x, src, np.zeros(1, np.int64), bad_init=3, expect_rc=1)
+    assert "exceed the LDS" in lib.lsm_gnn_last_error().decode()
 
 
 def check(lib, case, device=None, layouts=ga.LAYOUTS):

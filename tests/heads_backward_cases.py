@@ -23,6 +23,7 @@ import numpy as np
 import evaluate_cases as ec
 import evaluate_model as em
 import heads_backward_model as hm
+import launch_plans as lp
 import policy_cases as pc
 import policy_model as pm
 import recurrent_abi as ra
@@ -44,7 +45,8 @@ def seed_rows(cfg, R, seed):
     return (rng.normal(size=shape) / R).astype(np.float32)
 
 
-def run(lib, cfg, blob, inp, seed, Cn, T, device=None, dx=(True, True), expect_rc=0, over=None, add=None, alias=None):
+def run(lib, cfg, blob, inp, seed, Cn, T, device=None, dx=(True, True), expect_rc=0, over=None, add=None, alias=None,
+        workspace=False):
     """lsm_host_head_backward (device None) or lsm_head_backward on `device`. Returns {dweights, dx0, dx1} (the
     requested ones). over: replace io fields (by their header name), or 'cfg' / 'weights' / 'C' / 'T' / 'io';
     add: {field or 'weights': bytes added to that pointer}; alias: (field, other field, bytes). With
@@ -111,6 +113,8 @@ def run(lib, cfg, blob, inp, seed, Cn, T, device=None, dx=(True, True), expect_r
             continue
         if name != "workspace" and sizes[name]:
             got[name] = words[:sizes[name]].view(np.float32).copy()
+        if name == "workspace" and workspace:
+            got[name] = words            # every word the call was given (workspace=True: the raw int32 words)
     if expect_rc:
         assert err.startswith("backward: ") and len(err) > len("backward: "), err
     else:
@@ -163,6 +167,72 @@ def option_case(name):
     base, over = ec.OPTIONS[name]
     return admitted("option " + name, dataclasses.replace(base, **over), OPTION_C, OPTION_T,
                     1 + sorted(ec.OPTIONS).index(name))
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case(name):
+    """evaluate_cases.PLAN_OPTIONS for the backward: a 'max' is the backward's own limit (lsm_head_plan)."""
+    return admitted("plan " + name, ec.plan_cfg(name, "backward"), OPTION_C, ec.plan_T(name),
+                    30 + sorted(ec.PLAN_OPTIONS).index(name))
+
+
+def plan_of(name):
+    return lp.head_plan(ec.plan_cfg(name, "backward"), "backward", OPTION_C, ec.plan_T(name))[0]
+
+
+def plan_checks(lib, name, device):
+    """The case against the model; a case at an LDS limit also shows the next size refused, nothing written."""
+    case = plan_case(name)
+    check(lib, case, device)
+    past = ec.beyond(name, "backward") if name in ec.PLAN_LIMITS else None
+    if past is not None:
+        run(lib, past, np.zeros(400000, np.float32), em.random_inputs(past, 1, 1, 0), seed_rows(past, 1, 0), 1, 1,
+            device, expect_rc=1)
+        assert "bytes of LDS" in lib.lsm_policy_last_error().decode()
+
+
+def forward_is_evaluates(lib, case, device):
+    """Stage 1 of lsm_head_backward is lsm_head_evaluate's forward (the header's "the gradient is that of the
+    function lsm_head_evaluate computes"): on the same inputs the features it saved, and the last GRU layer's
+    h' at step T - 1, are evaluate's `features` and `rnn_out` to the byte. They are found in the workspace by
+    the header's layout ([T*C][hidden] arrays) at the offsets lsm_head_plan reports; the words behind the
+    documented size keep their canaries (run() checks the canaries around the buffer as well)."""
+    cfg, Cn, T, R, Hd, RN = case.cfg, case.C, case.T, case.R, case.cfg.hidden, case.cfg.recurrent_N
+    assert RN > 0
+    ev, _ = ec.run(lib, cfg, case.blob, case.inp, Cn, T, device, outputs=("features", "rnn_out"), scratch=False)
+    got = run(lib, cfg, case.blob, case.inp, case.dout, Cn, T, device, workspace=True)
+    ws = got["workspace"]
+    plan = lp.head_plan(cfg, "backward", Cn, T)[0]
+    assert len(ws) - plan["ws_floats"] in (0, 1) and (ws[plan["ws_floats"]:] == ra.CANARY).all()
+    assert not (ws[:plan["ws_floats"]] == ra.CANARY).all()
+    feat = ws[plan["o_feat"]:plan["o_feat"] + R * Hd].reshape(R, Hd)
+    np.testing.assert_array_equal(feat, ev["features"].view(np.int32), err_msg="the saved features")
+    top = plan["o_ho"][RN - 1]
+    last = ws[top:top + R * Hd].reshape(T, Cn, Hd)[T - 1]
+    np.testing.assert_array_equal(last, ev["rnn_out"][:, RN - 1].view(np.int32), err_msg="h' at step T - 1")
+    if RN == 2:
+        low = ws[plan["o_ho"][0]:plan["o_ho"][0] + R * Hd].reshape(T, Cn, Hd)[T - 1]
+        np.testing.assert_array_equal(low, ev["rnn_out"][:, 0].view(np.int32), err_msg="layer 0's h' at step T - 1")
+    compare({k: v for k, v in got.items() if k != "workspace"}, case, "backward %s" % case.name)
+
+
+def forward_cases():
+    """An actor recurrent_N 2 with zero masks, and a critic recurrent_N 1."""
+    return masks_case("actor"), shape_case("critic", 65, 10)
+
+
+# nin = 64, 65 and 128: the bias column alone in a job's second tile, beside one weight column, and alone in
+# its third (the accumulators a tile drops and the bias two-sum of the last tile, tied to the bytes)
+TWICE_PLAN = ("hidden64 rn1 max in", "hidden65", "in128")
+
+
+def plan_twice_checks(lib, name, device):
+    case = plan_case(name)
+    a = run(lib, case.cfg, case.blob, case.inp, case.dout, case.C, case.T, device)
+    b = run(lib, case.cfg, case.blob, case.inp, case.dout, case.C, case.T, device)
+    same_bytes(a, b, case.name)
+    c = run(lib, case.cfg, case.blob, case.inp, case.dout, case.C, case.T, device, dx=(False, False))
+    np.testing.assert_array_equal(c["dweights"].view(np.int32), a["dweights"].view(np.int32))
 
 
 @functools.lru_cache(maxsize=None)

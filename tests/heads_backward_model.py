@@ -83,7 +83,8 @@ class TorchBackward:
         s = torch.from_numpy(np.ascontiguousarray(seed)).to(self.dtype).reshape(o.shape)
         torch.autograd.backward([o], [s])
         out = {k: p.grad.detach().numpy().copy() for k, p in self.params.items()}
-        out["dx1"] = x1.grad.numpy().copy()
+        if x1.shape[1]:                      # in1 == 0: x1 is null and there is no dx1, as with x0
+            out["dx1"] = x1.grad.numpy().copy()
         if x0 is not None:
             out["dx0"] = x0.grad.numpy().copy()
         out["out"], out["pre"] = o.detach().numpy().copy(), pre

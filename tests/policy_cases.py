@@ -91,6 +91,23 @@ def option_case(name):
     return Case("option " + name, dataclasses.replace(base, **over), OPTION_M, seed=1 + sorted(OPTIONS).index(name))
 
 
+# The forward's own limits (lsm_head_plan, include/lsm_policy.h): its tile has no state rows, so the ABI's
+# limits (in 256, hidden 128) are its LDS limit too -- the largest tile the kernel's LDS is raised to -- and
+# in0 + in1 = 1 is the narrowest input row. tests/test_launch_plans.py walks the library to both.
+PLAN_OPTIONS = {
+    "hidden128 recurrent_N 2 in256": (ACTOR, dict(hidden=128, recurrent_N=2, in0=240)),
+    "critic hidden128 in256": (CRITIC, dict(hidden=128, in0=240)),
+    "in1": (ACTOR, dict(in0=0, in1=1, feature_norm=False)),
+    "in1 x1 null": (ACTOR, dict(in0=1, in1=0, feature_norm=False)),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case(name):
+    base, over = PLAN_OPTIONS[name]
+    return Case("plan " + name, dataclasses.replace(base, **over), OPTION_M, seed=40 + sorted(PLAN_OPTIONS).index(name))
+
+
 @functools.lru_cache(maxsize=None)
 def masks_case(kind):
     """Some rows' masks zero, with large finite garbage in their states."""

@@ -159,6 +159,13 @@ def test_host_options(lib, name):
     ec.check(lib, ec.option_case(name))
 
 
+@pytest.mark.parametrize("name", sorted(ec.PLAN_OPTIONS))
+def test_host_plan_cases(lib, name):
+    """One case per size limit and width class (evaluate_cases.PLAN_OPTIONS, the limits found through
+    lsm_head_plan); past an LDS limit the call is refused and writes nothing."""
+    ec.plan_checks(lib, name, None)
+
+
 @pytest.mark.parametrize("kind", ["actor", "critic"])
 def test_host_masked_state_does_not_leak(lib, kind):
     ec.masks_checks(lib, kind, None)

@@ -39,7 +39,7 @@ def test_exports_every_declared_symbol(lib):
     from lsm import build
     hdr = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
     declared = set(re.findall(r"^\s*(?:[\w\*]+\s+)+\**(lsm_\w+)\s*\(", hdr, re.M))
-    assert declared == set(capi.EXPORTED_GNN) and len(declared) == 4
+    assert declared == set(capi.EXPORTED_GNN) and len(declared) == 5
     for name in declared:
         assert hasattr(lib, name), name
         assert getattr(lib, name).argtypes is not None, name
@@ -158,6 +158,15 @@ def test_structure_expectation_covers_its_cases(lib):
 @pytest.mark.parametrize("name", sorted(gc.OPTIONS))
 def test_host_options(lib, name):
     gc.check(lib, gc.option_case(name))
+
+
+@pytest.mark.parametrize("name", sorted(gc.PLAN_CASES))
+def test_host_plan_cases(lib, name):
+    """One case per launch plan (gnn_cases.PLAN_CASES, sized from lsm_gnn_plan); a case at the largest accepted
+    E also shows E + 1 refused with nothing written."""
+    gc.check(lib, gc.plan_case(name))
+    if gc.PLAN_CASES[name][1] == "max":
+        gc.refused_beyond(lib, name)
 
 
 def test_host_ego_only_is_the_same_output(lib):

@@ -35,6 +35,15 @@ def test_options(lib, name):
     ec.check(lib, ec.option_case(name), DEV)
 
 
+@pytest.mark.parametrize("name", sorted(ec.PLAN_OPTIONS))
+def test_plan_cases(lib, name):
+    """One case per size limit and width class (evaluate_cases.PLAN_OPTIONS, the limits found through
+    lsm_head_plan): hidden 128, the widest inputs, the largest recurrent hidden (a tile of exactly 163840
+    bytes), layer_N 3 and 4, widths around 64 and 128, A above both widths and in0 + in1 = 1; past an LDS limit
+    the call is refused and writes nothing."""
+    ec.plan_checks(lib, name, DEV)
+
+
 @pytest.mark.parametrize("kind", ["actor", "critic"])
 def test_masked_state_does_not_leak(lib, kind):
     ec.masks_checks(lib, kind, DEV)

@@ -50,6 +50,16 @@ def test_options(lib, name):
     gc.check(lib, gc.option_case(name), DEV)
 
 
+@pytest.mark.parametrize("name", sorted(gc.PLAN_CASES))
+def test_plan_cases(lib, name):
+    """One case per launch plan (gnn_cases.PLAN_CASES, sized from lsm_gnn_plan): every team size, a graph count
+    the LDS cut (to 3 and to 1), both sides of the adjacency's move out of LDS in both instances, the largest
+    graphs and the widest config at its largest accepted E, with E + 1 refused and nothing written."""
+    gc.check(lib, gc.plan_case(name), DEV)
+    if gc.PLAN_CASES[name][1] == "max":
+        gc.refused_beyond(lib, name, DEV)
+
+
 def test_ego_row(lib):
     """agent_id differing per graph, 0 and E - 1 among them: each row is that node's, not another's."""
     case = gc.shape_case(24, 5)

@@ -37,6 +37,30 @@ def test_options(lib, name):
     hc.check(lib, hc.option_case(name), DEV)
 
 
+@pytest.mark.parametrize("name", ec.BACKWARD_PLAN_NAMES)
+def test_plan_cases(lib, name):
+    """One case per launch plan and size limit (evaluate_cases.PLAN_OPTIONS, the limits found through
+    lsm_head_plan): tiles of exactly 163840 bytes in the sweep (in 240 / 172 at hidden 64, in 248 at hidden
+    128), the largest recurrent hidden (88 / 76), stage-3 jobs with two and three tiles along i and more than
+    three along j, the bias column last in a tile and alone in the next, A above both widths, in0 + in1 = 1;
+    past an LDS limit the call is refused and writes nothing."""
+    hc.plan_checks(lib, name, DEV)
+
+
+@pytest.mark.parametrize("name", hc.TWICE_PLAN)
+def test_plan_cases_twice(lib, name):
+    """nin = 64, 65 and 128: the same call twice, and without dx0 / dx1, gives identical bytes."""
+    hc.plan_twice_checks(lib, name, DEV)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["actor recurrent_N 2 masks", "critic recurrent_N 1"])
+def test_backwards_forward_is_evaluates(lib, which):
+    """gru_layer_save is a second copy of gru_layer: the features stage 1 saved and the last GRU layer's h' at
+    step T - 1 are lsm_head_evaluate's `features` and `rnn_out` to the byte (workspace offsets from
+    lsm_head_plan), and the words behind the documented workspace size keep their canaries."""
+    hc.forward_is_evaluates(lib, hc.forward_cases()[which], DEV)
+
+
 @pytest.mark.parametrize("kind", ["actor", "critic"])
 def test_zero_masks(lib, kind):
     hc.check(lib, hc.masks_case(kind), DEV)

@@ -34,6 +34,13 @@ def test_options(lib, name):
     pc.check(lib, pc.option_case(name), DEV)
 
 
+@pytest.mark.parametrize("name", sorted(pc.PLAN_OPTIONS))
+def test_plan_cases(lib, name):
+    """The forward's largest tile (in 256, hidden 128: the bytes its LDS limit is raised to) and its narrowest
+    input row (in0 + in1 = 1, with x0 or x1 null)."""
+    pc.check(lib, pc.plan_case(name), DEV)
+
+
 @pytest.mark.parametrize("kind", ["actor", "critic"])
 def test_masked_state_does_not_leak(lib, kind):
     pc.masks_checks(lib, kind, DEV)

@@ -144,6 +144,25 @@ def test_host_options(lib, name):
     hc.check(lib, hc.option_case(name))
 
 
+@pytest.mark.parametrize("name", ec.BACKWARD_PLAN_NAMES)
+def test_host_plan_cases(lib, name):
+    """One case per launch plan and size limit (evaluate_cases.PLAN_OPTIONS, the limits found through
+    lsm_head_plan); past an LDS limit the call is refused and writes nothing."""
+    hc.plan_checks(lib, name, None)
+
+
+@pytest.mark.parametrize("name", hc.TWICE_PLAN)
+def test_host_plan_cases_twice(lib, name):
+    hc.plan_twice_checks(lib, name, None)
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["actor recurrent_N 2 masks", "critic recurrent_N 1"])
+def test_host_backwards_forward_is_evaluates(lib, which):
+    """lsm_host_head_backward's saved features and last h' are lsm_host_head_evaluate's outputs to the byte
+    (workspace offsets from lsm_head_plan)."""
+    hc.forward_is_evaluates(lib, hc.forward_cases()[which], None)
+
+
 @pytest.mark.parametrize("kind", ["actor", "critic"])
 def test_host_zero_masks(lib, kind):
     case = hc.masks_case(kind)

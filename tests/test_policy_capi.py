@@ -41,7 +41,7 @@ def test_exports_every_declared_symbol(lib):
     from lsm import build
     hdr = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
     declared = set(re.findall(r"^\s*(?:[\w\*]+\s+)+\**(lsm_\w+)\s*\(", hdr, re.M))
-    assert declared == set(capi.EXPORTED_POLICY) and len(declared) == 4
+    assert declared == set(capi.EXPORTED_POLICY) and len(declared) == 5
     for name in declared:
         assert hasattr(lib, name), name
         assert getattr(lib, name).argtypes is not None, name
@@ -171,6 +171,12 @@ def test_host_shapes(lib, kind, M):
 @pytest.mark.parametrize("name", sorted(pc.OPTIONS))
 def test_host_options(lib, name):
     pc.check(lib, pc.option_case(name))
+
+
+@pytest.mark.parametrize("name", sorted(pc.PLAN_OPTIONS))
+def test_host_plan_cases(lib, name):
+    """The forward's largest tile (in 256, hidden 128) and its narrowest input row (in0 + in1 = 1)."""
+    pc.check(lib, pc.plan_case(name))
 
 
 @pytest.mark.parametrize("kind", ["actor", "critic"])
