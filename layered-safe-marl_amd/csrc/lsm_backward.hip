@@ -6,11 +6,11 @@
 // them with a tile of one chunk and one "wave", and the same slab grouping.
 //
 // Stage 1, fwd_tile: lsm_evaluate.hip's eval_tile without the output layer (the seeds are given), with the
-// per-row pieces of csrc/lsm_head_tile.h, and with saves. A 256-thread workgroup owns 64 chunks, lane =
-// chunk, its four waves split each layer's columns, and the tile walks l = 0 .. T - 1. What a whole LDS row
-// holds after a barrier (the input of fc1, every activation and LayerNorm output, the masked state, h', the
-// features) is copied to workspace coalesced by all threads; the GRU's gates are written by the thread that
-// computed them (16 bytes per lane and column block).
+// pieces of csrc/lsm_head_tile.h (mlp and gru_layer through the hook Saves), and with saves. A 256-thread
+// workgroup owns 64 chunks, lane = chunk, its four waves split each layer's columns, and the tile walks l =
+// 0 .. T - 1. What a whole LDS row holds after a barrier (the input of fc1, every activation and LayerNorm
+// output, the masked state, h', the features) is copied to workspace coalesced by all threads; the GRU's gates
+// are written by the thread that computed them (16 bytes per lane and column block).
 //
 // Stage 2, bwd_tile: same ownership, l = T - 1 .. 0. Per chunk in LDS: B0 (a staged saved row, or the GRU's
 // four gate gradients E), B1 (a gradient row as wide as the input), B2 (a gradient row of Hd) and the state's
@@ -30,7 +30,6 @@
 // include/lsm_backward.h, then the slabs' partial blobs.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -69,120 +68,64 @@ struct Bwd : Shape {
   Job job[MAX_JOBS];
 };
 
-// rows m0 .. m0 + rows - 1 of a [R][n] array <- the tile's LDS rows, coalesced; the caller's barrier precedes
-LSM_HD void save_rows(const float* src, int stride, int n, float* dst, int64_t m0, int rows, int tid, int nt) {
-  for (int i = tid; i < rows * n; i += nt) {
-    const int r = i / n, c = i - r * n;
-    dst[m0 * n + i] = src[r * stride + c];
-  }
-}
-
-LSM_HD void load_rows(float* dst, int stride, int n, const float* src, int64_t m0, int rows, int tid, int nt) {
-  for (int i = tid; i < rows * n; i += nt) {
-    const int r = i / n, c = i - r * n;
-    dst[r * stride + c] = src[m0 * n + i];
-  }
-}
-
-// gru_layer of lsm_head_tile.h with the gates kept: r, z, n and hg = W_hn h + b_hn of row m to gr / gz / gg /
-// ghg (the [R][Hd] arrays; an idle lane writes nothing)
-LSM_HD void gru_layer_save(const Shape& n, const float* __restrict__ w, int l, const float* x, const float* h, float* o,
-                           int wv, int nw, bool active, int64_t m, float* gr, float* gz, float* gg, float* ghg) {
-  const int Hd = n.Hd;
-  const float* Wih = w + n.o_gru[l];
-  const float* Whh = Wih + 3 * Hd * Hd;
-  const float* bih = Whh + 3 * Hd * Hd;
-  const float* bhh = bih + 3 * Hd;
-  for (int j0 = 4 * wv; j0 < Hd; j0 += 4 * nw) {
-    const int nj = Hd - j0 < 4 ? Hd - j0 : 4;
-    float ir[4], iz[4], ig[4], hr[4], hz[4], hg[4];
-    bias4(bih + j0, nj, ir);
-    bias4(bih + Hd + j0, nj, iz);
-    bias4(bih + 2 * Hd + j0, nj, ig);
-    bias4(bhh + j0, nj, hr);
-    bias4(bhh + Hd + j0, nj, hz);
-    bias4(bhh + 2 * Hd + j0, nj, hg);
-    dot4(Wih + j0 * Hd, Hd, nj, x, Hd, ir);
-    dot4(Wih + (Hd + j0) * Hd, Hd, nj, x, Hd, iz);
-    dot4(Wih + (2 * Hd + j0) * Hd, Hd, nj, x, Hd, ig);
-    dot4(Whh + j0 * Hd, Hd, nj, h, Hd, hr);
-    dot4(Whh + (Hd + j0) * Hd, Hd, nj, h, Hd, hz);
-    dot4(Whh + (2 * Hd + j0) * Hd, Hd, nj, h, Hd, hg);
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      if (jj >= nj) continue;
-      const float r = sigmoid_(ir[jj] + hr[jj]);
-      const float z = sigmoid_(iz[jj] + hz[jj]);
-      const float g = tanhf(fma_(r, hg[jj], ig[jj]));
-      const float hp = fma_(z, h[j0 + jj], (1.0f - z) * g);
-      o[j0 + jj] = hp;
-      if (active) {
-        const int64_t at = m * Hd + j0 + jj;
-        gr[at] = r, gz[at] = z, gg[at] = g, ghg[at] = hg[jj];
-      }
-    }
-  }
-}
-
 // ---- stage 1: the forward with saves ------------------------------------------------------------------------
-// One tile: chunks b0 .. b0 + rows - 1, lane = chunk (lane >= rows: an idle lane that keeps the barriers
-// uniform and writes nothing), wave wv of nw; R = the tile's capacity in chunks. LDS as eval_tile's.
+
+// mlp's and gru_layer's hook for the tile's rows m0 ..: rows of X, nxt or cur to their [R][width] array of
+// the workspace, coalesced; the gates to theirs by the thread that computed them (an idle lane writes nothing)
+struct Saves {
+  const Bwd& n;
+  float* ws;
+  const float *X, *cur, *nxt;   // the tile's buffers as mlp sees them
+  int64_t m0;
+  int nrows, lane, tid, nt;
+  // the array's row m0 is the base, so that the index in the copy loop is the 32-bit i alone
+  LSM_HD void save(int64_t at, const float* tile, int stride, int width) const {
+    save_rows(tile, stride, width, ws + at + m0 * width, 0, nrows, tid, nt);
+  }
+  LSM_HD void rows(Saved which, int k) const {
+    if (which == SAVED_INPUT) save(n.o_u0, X, n.SX, n.in);
+    if (which == SAVED_ACT) save(n.o_p[k], nxt, n.SA, n.Hd);
+    if (which == SAVED_NORM) save(n.o_y[k], cur, n.SA, n.Hd);
+  }
+  LSM_HD void gates(int k, int j, float r, float z, float g, float hg) const {
+    if (lane >= nrows) return;
+    const int64_t at = (m0 + lane) * n.Hd + j;
+    ws[n.o_r[k] + at] = r, ws[n.o_z[k] + at] = z, ws[n.o_g[k] + at] = g, ws[n.o_hg[k] + at] = hg;
+  }
+};
+
+// One tile, eval_tile's arguments and LDS
 LSM_HD void fwd_tile(const Bwd& n, const float* __restrict__ w, int64_t b0, int rows, int lane, int wv, int nw, int R,
                      float* lds) {
   const int tid = wv * R + lane, nt = nw * R;
   const int Hd = n.Hd, SX = n.SX, SA = n.SA, SH = n.SH, RN = n.RN;
-  float* ws = static_cast<float*>(n.io.workspace);
   float* X = lds;
   float* cur = X + R * SX;
   float* nxt = cur + R * SA;
   float* H = nxt + R * SA;   // [RN][R][SH]
-  const bool active = lane < rows;
-  float* xrow = X + lane * SX;
 
   for (int k = 0; k < RN; ++k)
-    for (int i = tid; i < rows * Hd; i += nt) {
-      const int r = i / Hd, c = i - r * Hd;
-      H[(k * R + r) * SH + c] = n.io.rnn_states[((b0 + r) * RN + k) * Hd + c];
-    }
+    load_rows(H + k * R * SH, SH, Hd, n.io.rnn_states + k * Hd, b0, rows, tid, nt, (RN - 1) * Hd);
 
   for (int l = 0; l < n.T; ++l) {
     const int64_t m0 = (int64_t)l * n.C + b0;
-    const int64_t m = m0 + lane;
+    const Saves keep{n, static_cast<float*>(n.io.workspace), X, cur, nxt, m0, rows, lane, tid, nt};
     load_inputs(n, n.io.x0, n.io.x1, m0, rows, X, tid, nt);
     LSM_SYNC();
-    if (n.fnorm) {
-      layer_norm(xrow, xrow, n.in, w + n.o_fn, w + n.o_fn + n.in, wv, nw);
-      LSM_SYNC();
-    }
-    save_rows(X, SX, n.in, ws + n.o_u0, m0, rows, tid, nt);
-    for (int k = 0; k <= n.L; ++k) {
-      const int din = k == 0 ? n.in : Hd;
-      const float* W = w + n.o_fc[k];
-      const float* b = W + Hd * din;
-      linear(W, b, Hd, din, k == 0 ? xrow : cur + lane * SA, nxt + lane * SA, wv, nw, n.relu ? 1 : 2);
-      LSM_SYNC();
-      save_rows(nxt, SA, Hd, ws + n.o_p[k], m0, rows, tid, nt);
-      layer_norm(nxt + lane * SA, cur + lane * SA, Hd, b + Hd, b + 2 * Hd, wv, nw);
-      LSM_SYNC();
-      save_rows(cur, SA, Hd, ws + n.o_y[k], m0, rows, tid, nt);
-    }
+    mlp(n, w, X + lane * SX, cur + lane * SA, nxt + lane * SA, wv, nw, keep);
     for (int k = 0; k < RN; ++k) {
       float* Hk = H + k * R * SH;
-      for (int i = tid; i < rows * Hd; i += nt) {
-        const int r = i / Hd, c = i - r * Hd;
-        Hk[r * SH + c] = Hk[r * SH + c] * n.io.masks[m0 + r];
-      }
+      load_rows(Hk, SH, Hd, Hk, 0, rows, tid, nt, SH - Hd, TimesRow{n.io.masks, m0});   // h_k *= mask
       LSM_SYNC();
-      save_rows(Hk, SH, Hd, ws + n.o_hm[k], m0, rows, tid, nt);
-      gru_layer_save(n, w, k, cur + lane * SA, Hk + lane * SH, nxt + lane * SA, wv, nw, active, m, ws + n.o_r[k],
-                     ws + n.o_z[k], ws + n.o_g[k], ws + n.o_hg[k]);
+      keep.save(n.o_hm[k], Hk, SH, Hd);
+      gru_layer(n, w, k, cur + lane * SA, Hk + lane * SH, nxt + lane * SA, wv, nw, keep);
       LSM_SYNC();
       float* t = cur;
       cur = nxt;
       nxt = t;
       for (int j0 = 4 * wv; j0 < Hd; j0 += 4 * nw)
         for (int j = j0; j < Hd && j < j0 + 4; ++j) Hk[lane * SH + j] = cur[lane * SA + j];
-      save_rows(cur, SA, Hd, ws + n.o_ho[k], m0, rows, tid, nt);
+      keep.save(n.o_ho[k], cur, SA, Hd);
     }
     if (RN > 0) {
       layer_norm(cur + lane * SA, nxt + lane * SA, Hd, w + n.o_rn, w + n.o_rn + Hd, wv, nw);
@@ -199,7 +142,7 @@ LSM_HD void fwd_tile(const Bwd& n, const float* __restrict__ w, int64_t b0, int 
       }
       LSM_SYNC();
     }
-    save_rows(cur, SA, Hd, ws + n.o_feat, m0, rows, tid, nt);
+    keep.save(n.o_feat, cur, SA, Hd);
     // the next step writes cur only after two barriers
   }
 }
@@ -534,21 +477,13 @@ LSM_HD void finish_entry(const Bwd& n, int64_t e) {
 }
 
 __global__ __launch_bounds__(BLOCK) void fwd_kernel(Bwd n, const float* __restrict__ w) {
-  extern __shared__ float4 lds4[];
-  const int64_t b0 = (int64_t)blockIdx.x * TILE;
-  const int64_t left = n.C - b0;
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TILE);
-  fwd_tile(n, w, b0, left < TILE ? (int)left : TILE, (int)threadIdx.x & (TILE - 1), wv, WAVES, TILE,
-           reinterpret_cast<float*>(lds4));
+  const Tile t = block_tile(n.C);
+  fwd_tile(n, w, t.row0, t.rows, t.lane, t.wv, WAVES, TILE, t.lds);
 }
 
 __global__ __launch_bounds__(BLOCK) void bwd_kernel(Bwd n, const float* __restrict__ w) {
-  extern __shared__ float4 lds4[];
-  const int64_t b0 = (int64_t)blockIdx.x * TILE;
-  const int64_t left = n.C - b0;
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TILE);
-  bwd_tile(n, w, b0, left < TILE ? (int)left : TILE, (int)threadIdx.x & (TILE - 1), wv, WAVES, TILE,
-           reinterpret_cast<float*>(lds4));
+  const Tile t = block_tile(n.C);
+  bwd_tile(n, w, t.row0, t.rows, t.lane, t.wv, WAVES, TILE, t.lds);
 }
 
 __global__ __launch_bounds__(BLOCK) void dw_kernel(Bwd n) {
@@ -560,29 +495,16 @@ __global__ __launch_bounds__(BLOCK) void finish_kernel(Bwd n) {
   if (e < n.NW) finish_entry(n, e);
 }
 
-int fail(const char* msg) {
-  lsm_policy_set_error("backward: ", msg);
-  return 1;
-}
-
-int64_t groups_of(int64_t C) { return (C + TILE - 1) / TILE; }
+int fail(const char* msg) { return refuse("backward: ", msg); }
 
 size_t fwd_tile_floats(const Bwd& n) { return (size_t)n.SX + 2 * (size_t)n.SA + (size_t)n.RN * n.SH; }
 size_t bwd_tile_floats(const Bwd& n) { return (size_t)n.S0 + n.S1 + n.S2 + (size_t)n.RN * n.SH; }
-
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  if (!a || !b || na == 0 || nb == 0) return false;
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + nb && y < x + na;
-}
 
 // the config's and the sizes' part of a call: the LDS strides, the workspace layout and the jobs; 0 when fine
 int make_plan(const lsm_head_config& c, int64_t C, int32_t T, Bwd* n) {
   const size_t nw = layout(c, n, "backward: ");
   if (nw == 0) return 1;
-  if (T < 1) return fail("T < 1");
-  if (C < 0) return fail("C < 0");
-  if (C > INT32_MAX / (int64_t)T) return fail("T * C exceeds INT32_MAX rows; split the minibatch");
+  if (check_sizes("backward: ", "C", "T * C", "minibatch", C, T)) return 1;
   const int Hd = n->Hd, in = n->in, A = n->A, L = n->L, RN = n->RN;
   n->NW = (int64_t)nw;
   n->C = C;
@@ -596,8 +518,7 @@ int make_plan(const lsm_head_config& c, int64_t C, int32_t T, Bwd* n) {
   n->S0 = pad(in > g ? in : g);
   n->S1 = pad(in > Hd ? (in > A ? in : A) : (Hd > A ? Hd : A));
   n->S2 = pad(Hd);
-  const size_t need1 = (size_t)TILE * fwd_tile_floats(*n) * sizeof(float);
-  const size_t need2 = (size_t)TILE * bwd_tile_floats(*n) * sizeof(float);
+  const size_t need1 = tile_bytes(fwd_tile_floats(*n)), need2 = tile_bytes(bwd_tile_floats(*n));
   if (need1 > (size_t)WORKGROUP_LDS_BYTES || need2 > (size_t)WORKGROUP_LDS_BYTES) {
     char msg[240];
     snprintf(msg, sizeof msg,
@@ -670,24 +591,23 @@ int make_bwd(const lsm_head_config& c, const float* weights, const lsm_bwd_io* i
   if (!io) return fail("io is null");
   lsm_bwd_io f = *io;
   const bool actor = n->kind == LSM_HEAD_ACTOR;
-  if (n->in0 == 0) f.x0 = nullptr, f.dx0 = nullptr;
-  if (n->in1 == 0) f.x1 = nullptr, f.dx1 = nullptr;
-  if (n->RN == 0) f.rnn_states = f.masks = nullptr;
+  drop_unread(*n, &f);
+  if (n->in0 == 0) f.dx0 = nullptr;
+  if (n->in1 == 0) f.dx1 = nullptr;
   if (actor)
     f.dvalues = nullptr;
   else
     f.dlogits = f.available_actions = nullptr;
   if (!f.dweights) return fail("dweights is null");
   if (!f.workspace) return fail("workspace is null");
-  if (C > 0 && ((n->in0 > 0 && !f.x0) || (n->in1 > 0 && !f.x1))) return fail("x0 / x1 is null");
-  if (C > 0 && n->RN > 0 && (!f.rnn_states || !f.masks)) return fail("the recurrent form needs rnn_states and masks");
+  if (const char* why = inputs_missing(*n, f, C)) return fail(why);
+  if (const char* why = states_missing(*n, f, C)) return fail(why);
   if (C > 0 && actor && !f.dlogits) return fail("the actor needs dlogits");
   if (C > 0 && !actor && !f.dvalues) return fail("the critic needs dvalues");
-  const void* p4[] = {weights, f.x0, f.x1, f.rnn_states, f.masks, f.available_actions, f.dlogits, f.dvalues, f.dweights,
-                      f.dx0, f.dx1};
-  for (const void* p : p4)
-    if ((uintptr_t)p & 3) return fail("misaligned pointer");
-  if ((uintptr_t)f.workspace & 7) return fail("misaligned pointer (workspace: 8 bytes)");
+  if (const char* why = misaligned({weights, f.x0, f.x1, f.rnn_states, f.masks, f.available_actions, f.dlogits,
+                                    f.dvalues, f.dweights, f.dx0, f.dx1}))
+    return fail(why);
+  if (const char* why = misaligned({f.workspace}, 7, "misaligned pointer (workspace: 8 bytes)")) return fail(why);
   const size_t F = sizeof(float), R = (size_t)n->R;
   struct Range {
     const void* p;
@@ -707,9 +627,9 @@ int make_bwd(const lsm_head_config& c, const float* weights, const lsm_bwd_io* i
                        {f.dvalues, R * F}};
   for (int a = 0; a < 4; ++a) {
     for (const Range& b : ins)
-      if (ranges_overlap(outs[a].p, outs[a].bytes, b.p, b.bytes)) return fail("an output overlaps an input");
+      if (overlap(outs[a].p, outs[a].bytes, b.p, b.bytes)) return fail("an output overlaps an input");
     for (int b = a + 1; b < 4; ++b)
-      if (ranges_overlap(outs[a].p, outs[a].bytes, outs[b].p, outs[b].bytes)) return fail("two outputs overlap");
+      if (overlap(outs[a].p, outs[a].bytes, outs[b].p, outs[b].bytes)) return fail("two outputs overlap");
   }
   n->w = weights;
   n->io = f;
@@ -725,8 +645,8 @@ int lsm_backward_fill_plan(const lsm_head_config& c, int64_t C, int32_t T, lsm_h
   out->SX = n.SX, out->SA = n.SA, out->SH = n.SH;
   out->S0 = n.S0, out->S1 = n.S1, out->S2 = n.S2, out->HP = n.HP;
   out->njobs = n.njobs, out->ntiles = n.ntiles;
-  out->lds_bytes[0] = (int64_t)((size_t)TILE * fwd_tile_floats(n) * sizeof(float));
-  out->lds_bytes[1] = (int64_t)((size_t)TILE * bwd_tile_floats(n) * sizeof(float));
+  out->lds_bytes[0] = (int64_t)tile_bytes(fwd_tile_floats(n));
+  out->lds_bytes[1] = (int64_t)tile_bytes(bwd_tile_floats(n));
   out->slabs = n.slabs;
   out->ws_floats = n.ws_floats;
   out->o_feat = n.o_feat;
@@ -752,20 +672,16 @@ int lsm_head_backward(lsm_head_config cfg, const float* weights, const lsm_bwd_i
   Bwd n;
   if (make_bwd(cfg, weights, io, C, T, &n)) return 1;
   if (C == 0) return 0;
-  hipStream_t st = (hipStream_t)hip_stream;
-  const dim3 grid((unsigned)groups_of(C)), block(BLOCK);
-  static std::atomic<bool> raised1[MAX_DEVICES], raised2[MAX_DEVICES];   // to a workgroup's whole LDS
-  if (const char* why = raise_lds_once(raised1, (const void*)fwd_kernel, WORKGROUP_LDS_BYTES)) return fail(why);
-  if (const char* why = raise_lds_once(raised2, (const void*)bwd_kernel, WORKGROUP_LDS_BYTES)) return fail(why);
-  fwd_kernel<<<grid, block, (size_t)TILE * fwd_tile_floats(n) * sizeof(float), st>>>(n, n.w);
-  if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  bwd_kernel<<<grid, block, (size_t)TILE * bwd_tile_floats(n) * sizeof(float), st>>>(n, n.w);
-  if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  dw_kernel<<<dim3((unsigned)n.slabs, (unsigned)n.ntiles), block, 0, st>>>(n);
-  if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  finish_kernel<<<dim3((unsigned)((n.NW + BLOCK - 1) / BLOCK)), block, 0, st>>>(n);
-  if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  return 0;
+  const dim3 grid((unsigned)tiles_of(C));
+  const size_t lds1 = tile_bytes(fwd_tile_floats(n)), lds2 = tile_bytes(bwd_tile_floats(n));
+  // the LDS limits: to a workgroup's whole LDS
+  const char* why = raise_lds<fwd_kernel, WORKGROUP_LDS_BYTES>();
+  if (!why) why = raise_lds<bwd_kernel, WORKGROUP_LDS_BYTES>();
+  if (!why) why = launch<fwd_kernel, WORKGROUP_LDS_BYTES>(grid, BLOCK, lds1, hip_stream, n, n.w);
+  if (!why) why = launch<bwd_kernel, WORKGROUP_LDS_BYTES>(grid, BLOCK, lds2, hip_stream, n, n.w);
+  if (!why) why = launch<dw_kernel>(dim3((unsigned)n.slabs, (unsigned)n.ntiles), BLOCK, 0, hip_stream, n);
+  if (!why) why = launch<finish_kernel>((unsigned)((n.NW + BLOCK - 1) / BLOCK), BLOCK, 0, hip_stream, n);
+  return why ? fail(why) : 0;
 }
 
 int lsm_host_head_backward(lsm_head_config cfg, const float* weights, const lsm_bwd_io* io, int64_t C, int32_t T) {
@@ -774,9 +690,8 @@ int lsm_host_head_backward(lsm_head_config cfg, const float* weights, const lsm_
   if (C == 0) return 0;
   const size_t f1 = fwd_tile_floats(n), f2 = bwd_tile_floats(n);
   std::vector<float4> lds((f1 > f2 ? f1 : f2) / 4 + 1);
-  float* l = reinterpret_cast<float*>(lds.data());
-  for (int64_t b = 0; b < C; ++b) fwd_tile(n, n.w, b, 1, 0, 0, 1, 1, l);
-  for (int64_t b = 0; b < C; ++b) bwd_tile(n, n.w, b, 1, 0, 0, 1, 1, l);
+  for (int64_t b = 0; b < C; ++b) fwd_tile(n, n.w, b, 1, 0, 0, 1, 1, reinterpret_cast<float*>(lds.data()));
+  for (int64_t b = 0; b < C; ++b) bwd_tile(n, n.w, b, 1, 0, 0, 1, 1, reinterpret_cast<float*>(lds.data()));
   for (int64_t s = 0; s < n.slabs; ++s)
     for (int t = 0; t < n.ntiles; ++t)
       for (int tid = 0; tid < BLOCK; ++tid) dw_thread(n, t, s, tid);

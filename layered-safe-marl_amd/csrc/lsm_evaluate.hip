@@ -20,10 +20,11 @@
 // to scratch; finish_kernel (one thread) adds the groups in order and divides.
 //
 // eval_tile is ONE __host__ __device__ text; lsm_host_head_evaluate runs it with a tile of one chunk and one
-// "wave", and adds the chunks' sums in the kernel's grouping.
+// "wave", and adds the chunks' sums in the kernel's grouping. Its step and copy loops stand here in full:
+// eval_kernel is kept byte-identical, and reaching them through shared functions changes its code. Stage 1
+// of lsm_backward.hip restates the step with saves; test_backwards_forward_is_evaluates holds the two to one.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -185,25 +186,15 @@ LSM_HD void finish(const double* scratch, int64_t groups, float* dist_entropy) {
 }
 
 __global__ __launch_bounds__(BLOCK) void eval_kernel(Eval n, const float* __restrict__ w) {
-  extern __shared__ float4 lds4[];
-  const int64_t b0 = (int64_t)blockIdx.x * TILE;
-  const int64_t left = n.C - b0;
-  // the wave's index as a scalar: the weight addresses derived from it are then lane-uniform to the compiler
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TILE);
-  eval_tile(n, w, b0, left < TILE ? (int)left : TILE, (int)threadIdx.x & (TILE - 1), wv, WAVES, TILE,
-            reinterpret_cast<float*>(lds4), n.io.scratch + 2 * (int64_t)blockIdx.x);
+  const Tile t = block_tile(n.C);
+  eval_tile(n, w, t.row0, t.rows, t.lane, t.wv, WAVES, TILE, t.lds, n.io.scratch + 2 * (int64_t)blockIdx.x);
 }
 
 __global__ void finish_kernel(const double* scratch, int64_t groups, float* dist_entropy) {
   if (blockIdx.x == 0 && threadIdx.x == 0) finish(scratch, groups, dist_entropy);
 }
 
-int fail(const char* msg) {
-  lsm_policy_set_error("evaluate: ", msg);
-  return 1;
-}
-
-int64_t groups_of(int64_t C) { return (C + TILE - 1) / TILE; }
+int fail(const char* msg) { return refuse("evaluate: ", msg); }
 
 size_t tile_floats(const Eval& n) { return (size_t)n.SX + 2 * (size_t)n.SA + (size_t)n.RN * n.SH; }
 
@@ -211,7 +202,7 @@ size_t tile_floats(const Eval& n) { return (size_t)n.SX + 2 * (size_t)n.SA + (si
 int make_shape(const lsm_head_config& c, Eval* n) {
   if (layout(c, n, "evaluate: ") == 0) return 1;
   n->SH = pad(n->Hd);
-  const size_t need = (size_t)TILE * tile_floats(*n) * sizeof(float);
+  const size_t need = tile_bytes(tile_floats(*n));
   if (need > (size_t)WORKGROUP_LDS_BYTES) {
     char msg[200];
     snprintf(msg, sizeof msg,
@@ -223,24 +214,17 @@ int make_shape(const lsm_head_config& c, Eval* n) {
   return 0;
 }
 
-int check_sizes(int64_t C, int32_t T) {
-  if (T < 1) return fail("T < 1");
-  if (C < 0) return fail("C < 0");
-  if (C > INT32_MAX / (int64_t)T) return fail("T * C exceeds INT32_MAX rows; split the minibatch");
-  return 0;
-}
+int check_rows(int64_t C, int32_t T) { return check_sizes("evaluate: ", "C", "T * C", "minibatch", C, T); }
 
 // every check of one call, shared by the device and the host entry point; fills n; 0 when fine
 int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io* io, int64_t C, int32_t T, Eval* n) {
   if (make_shape(c, n)) return 1;
   if (!weights) return fail("weights is null");
   if (!io) return fail("io is null");
-  if (check_sizes(C, T)) return 1;
-  // the fields this config does not read or write are dropped first: they are not checked either
+  if (check_rows(C, T)) return 1;
   lsm_eval_io f = *io;
-  if (n->in0 == 0) f.x0 = nullptr;
-  if (n->in1 == 0) f.x1 = nullptr;
-  if (n->RN == 0) f.rnn_states = f.masks = nullptr, f.rnn_out = nullptr;
+  drop_unread(*n, &f);
+  if (n->RN == 0) f.rnn_out = nullptr;
   if (n->kind == LSM_HEAD_ACTOR) {
     f.values = nullptr;
   } else {
@@ -248,18 +232,11 @@ int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io*
     f.log_probs = f.entropy = f.dist_entropy = f.logits = nullptr;
     f.scratch = nullptr;
   }
-  if (C > 0 && ((n->in0 > 0 && !f.x0) || (n->in1 > 0 && !f.x1))) return fail("x0 / x1 is null");
-  const void* p4[] = {weights,     f.x0,      f.x1,           f.rnn_states, f.masks,  f.actions,  f.available_actions,
-                      f.active_masks, f.log_probs, f.entropy, f.dist_entropy, f.logits, f.values, f.features,
-                      f.rnn_out};
-  for (const void* p : p4)
-    if ((uintptr_t)p & 3) return fail("misaligned pointer");
-  if (((uintptr_t)f.bad & 7) || ((uintptr_t)f.scratch & 7)) return fail("misaligned pointer (bad and scratch: 8 bytes)");
-  if (n->RN > 0) {
-    if (C > 0 && (!f.rnn_states || !f.masks)) return fail("the recurrent form needs rnn_states and masks");
-    if (f.rnn_out && C > 0 && overlap(f.rnn_out, f.rnn_states, (size_t)C * n->RN * n->Hd * sizeof(float)))
-      return fail("rnn_out overlaps rnn_states");
-  }
+  const char* why = check_io(*n, weights, f, C,
+                             {f.actions, f.available_actions, f.active_masks, f.log_probs, f.entropy, f.dist_entropy,
+                              f.logits, f.values},
+                             {f.bad, f.scratch}, "misaligned pointer (bad and scratch: 8 bytes)");
+  if (why) return fail(why);
   if (n->kind == LSM_HEAD_ACTOR) {
     if (C > 0 && !f.actions) return fail("the actor needs actions");
     if (!f.log_probs && !f.entropy && !f.dist_entropy && !f.logits && !f.features && !f.rnn_out)
@@ -277,9 +254,9 @@ int make_eval(const lsm_head_config& c, const float* weights, const lsm_eval_io*
 
 int lsm_evaluate_fill_plan(const lsm_head_config& c, int64_t C, int32_t T, lsm_head_launch_plan* out) {
   Eval n;
-  if (make_shape(c, &n) || check_sizes(C, T)) return 1;
+  if (make_shape(c, &n) || check_rows(C, T)) return 1;
   out->SX = n.SX, out->SA = n.SA, out->SH = n.SH;
-  out->lds_bytes[0] = (int64_t)((size_t)TILE * tile_floats(n) * sizeof(float));
+  out->lds_bytes[0] = (int64_t)tile_bytes(tile_floats(n));
   return 0;
 }
 
@@ -287,7 +264,7 @@ extern "C" {
 
 size_t lsm_head_evaluate_scratch_bytes(int64_t C, int32_t T) {
   if (C < 0 || T < 1) return 0;
-  const int64_t g = groups_of(C);
+  const int64_t g = tiles_of(C);
   return (size_t)(g < 1 ? 1 : g) * 2 * sizeof(double);
 }
 
@@ -296,17 +273,12 @@ int lsm_head_evaluate(lsm_head_config cfg, const float* weights, const lsm_eval_
   Eval n;
   if (make_eval(cfg, weights, io, C, T, &n)) return 1;
   if (C == 0) return 0;
-  const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
-  const dim3 grid((unsigned)groups_of(C)), block(BLOCK);
-  static std::atomic<bool> raised[MAX_DEVICES];   // to a workgroup's whole LDS
-  if (const char* why = raise_lds_once(raised, (const void*)eval_kernel, WORKGROUP_LDS_BYTES)) return fail(why);
-  eval_kernel<<<grid, block, lds, (hipStream_t)hip_stream>>>(n, n.w);
-  if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  if (n.io.dist_entropy) {
-    finish_kernel<<<1, 1, 0, (hipStream_t)hip_stream>>>(n.io.scratch, groups_of(C), n.io.dist_entropy);
-    if (hipGetLastError() != hipSuccess) return fail("launch failed");
-  }
-  return 0;
+  // the LDS limit: to a workgroup's whole LDS
+  const char* why = launch<eval_kernel, WORKGROUP_LDS_BYTES>((unsigned)tiles_of(C), BLOCK, tile_bytes(tile_floats(n)),
+                                                             hip_stream, n, n.w);
+  if (!why && n.io.dist_entropy)
+    why = launch<finish_kernel>(1, 1, 0, hip_stream, (const double*)n.io.scratch, tiles_of(C), n.io.dist_entropy);
+  return why ? fail(why) : 0;
 }
 
 int lsm_host_head_evaluate(lsm_head_config cfg, const float* weights, const lsm_eval_io* io, int64_t C, int32_t T) {
@@ -314,7 +286,7 @@ int lsm_host_head_evaluate(lsm_head_config cfg, const float* weights, const lsm_
   if (make_eval(cfg, weights, io, C, T, &n)) return 1;
   if (C == 0) return 0;
   std::vector<float4> lds(tile_floats(n) / 4 + 1);
-  for (int64_t g = 0; g < groups_of(C); ++g) {
+  for (int64_t g = 0; g < tiles_of(C); ++g) {
     double e = 0.0, wsum = 0.0;   // the group's sums: its chunks in order, as the kernel's thread 0 adds its lanes
     for (int64_t b = g * TILE; b < C && b < (g + 1) * TILE; ++b) {
       double part[2] = {0.0, 0.0};
@@ -323,7 +295,7 @@ int lsm_host_head_evaluate(lsm_head_config cfg, const float* weights, const lsm_
     }
     if (n.io.dist_entropy) n.io.scratch[2 * g] = e, n.io.scratch[2 * g + 1] = wsum;
   }
-  if (n.io.dist_entropy) finish(n.io.scratch, groups_of(C), n.io.dist_entropy);
+  if (n.io.dist_entropy) finish(n.io.scratch, tiles_of(C), n.io.dist_entropy);
   return 0;
 }
 

@@ -1,8 +1,11 @@
-// lsm_head_tile.h -- the per-row pieces of the actor / critic heads that the one-step kernel
-// (lsm_policy.hip, include/lsm_policy.h) and the sequence kernel (lsm_evaluate.hip, include/lsm_evaluate.h)
-// both run: the config's checks and the weight blob's offsets, dot4 / linear / layer_norm, the input
-// staging, MLPBase, one GRU layer's cells and the masked softmax's first two walks. Every function is ONE
-// __host__ __device__ text: the host entry points run it with a tile of one row and one "wave".
+// lsm_head_tile.h -- what the three head units share (lsm_policy.hip: one step; lsm_evaluate.hip: the sequence
+// form; lsm_backward.hip: the backward pass). Device side: the kernels' entry (block_tile), the tile-row
+// copies (load_rows, save_rows), dot4 / linear / layer_norm, the input staging, MLPBase, one GRU layer's cells
+// and the softmax walks. MLPBase and the GRU cells take a hook (NoSaves by default: nothing kept, nothing
+// paid) through which stage 1 of the backward keeps what its sweep needs. Host side: the config's checks and
+// the weight blob's offsets, the checks of a call that the units share (each unit keeps its own order of
+// them) and launch(). Every device piece is ONE __host__ __device__ text: the host entry points run it with a
+// tile of one row and one "wave".
 //
 // Work split and LDS layout are described in lsm_policy.hip; what a piece expects of the barriers around
 // it stands at the piece.
@@ -16,6 +19,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "../../include/lsm_policy.h"
 
@@ -58,11 +62,55 @@ inline const char* raise_lds_once(std::atomic<bool> (&raised)[MAX_DEVICES], cons
   return nullptr;
 }
 
+// One launch on the stream: Kernel's dynamic-LDS limit raised to LdsLimit bytes first (raise_lds: once per
+// device, the flags being that instantiation's own; 0: the kernel has no dynamic LDS), the launch, its check.
+// Returns nullptr, or the refusal's text. A call of several kernels raises every limit before its first launch.
+template <auto Kernel, int LdsLimit>
+const char* raise_lds() {
+  static std::atomic<bool> raised[MAX_DEVICES];
+  return raise_lds_once(raised, (const void*)Kernel, LdsLimit);
+}
+
+template <auto Kernel, int LdsLimit = 0, class... Args>
+const char* launch(dim3 grid, dim3 block, size_t lds, void* hip_stream, const Args&... args) {
+  if constexpr (LdsLimit > 0)
+    if (const char* why = raise_lds<Kernel, LdsLimit>()) return why;
+  Kernel<<<grid, block, lds, (hipStream_t)hip_stream>>>(args...);
+  return hipGetLastError() == hipSuccess ? nullptr : "launch failed";
+}
+
 // the head's shape and the offsets of its weights in the packed blob
 struct Shape {
   int32_t in0, in1, in, Hd, L, relu, fnorm, RN, kind, A;
   int32_t SX, SA;          // padded LDS row strides: the input row, an activation row
   int32_t o_fn, o_fc[MAX_LAYERS + 1], o_gru[MAX_RNN], o_rn, o_out;
+};
+
+// A kernel's entry: this block's tile of a call of total rows, as the tile functions' leading arguments (rows
+// row0 .. row0 + rows - 1, lane = row, the wave's index, the tile's LDS)
+struct Tile {
+  int64_t row0;
+  int rows, lane, wv;
+  float* lds;
+};
+
+__device__ __forceinline__ Tile block_tile(int64_t total) {
+  extern __shared__ float4 lds4[];
+  const int64_t row0 = (int64_t)blockIdx.x * TILE;
+  const int64_t left = total - row0;
+  // the wave's index as a scalar: the weight addresses derived from it are then lane-uniform to the compiler
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TILE);
+  return {row0, left < TILE ? (int)left : TILE, (int)threadIdx.x & (TILE - 1), wv, reinterpret_cast<float*>(lds4)};
+}
+
+// What MLPBase and a GRU layer hand out on their way, for lsm_backward.hip's stage 1 to keep. rows(): the
+// tile's rows of layer k's array are whole (every thread calls it behind the barrier; the hook knows the
+// buffers). gates(): GRU layer l's r, z, n and hg = W_hn h + b_hn of column j, from the thread that computed
+// them. The default keeps nothing and compiles to nothing.
+enum Saved { SAVED_INPUT, SAVED_ACT, SAVED_NORM };   // fc1's input (X), a layer's activation (nxt), its norm (cur)
+struct NoSaves {
+  LSM_HD void rows(Saved, int) const {}
+  LSM_HD void gates(int, int, float, float, float, float) const {}
 };
 
 LSM_HD float fma_(float a, float b, float c) {
@@ -186,45 +234,76 @@ LSM_HD void layer_norm(const float* src, float* dst, int n, const float* __restr
     for (int j = j0; j < n && j < j0 + 4; ++j) dst[j] = fma_((src[j] - mean) * rs, gamma[j], beta[j]);
 }
 
+// The tile-row copies, by all of the tile's threads, consecutive threads on consecutive floats of a row: n
+// floats of each of rows rows, between LDS rows stride floats apart (from column col on) and rows m0 .. of a
+// global array whose rows are n + gap floats apart. Float i is column c of row r: LDS index r * stride + col
+// + c, global index m0 * n + i + (m0 + r) * gap (gap 0, a [.][n] array: m0 * n + i). The caller's barrier
+// precedes save_rows and follows load_rows. load_rows reads through f(value, r): nothing, or a row's factor.
+struct AsIs {
+  LSM_HD float operator()(float v, int) const { return v; }
+};
+struct TimesRow {   // factor[m0 + r]: a [.] array's rows m0 ..
+  const float* factor;
+  int64_t m0;
+  LSM_HD float operator()(float v, int r) const { return v * factor[m0 + r]; }
+};
+
+LSM_HD void save_rows(const float* src, int stride, int n, float* dst, int64_t m0, int rows, int tid, int nt,
+                      int gap = 0, int col = 0) {
+  for (int i = tid; i < rows * n; i += nt) {
+    const int r = i / n, c = i - r * n;
+    dst[m0 * n + i + (m0 + r) * gap] = src[r * stride + col + c];
+  }
+}
+
+template <class F = AsIs>
+LSM_HD void load_rows(float* dst, int stride, int n, const float* src, int64_t m0, int rows, int tid, int nt,
+                      int gap = 0, F f = {}, int col = 0) {
+  for (int i = tid; i < rows * n; i += nt) {
+    const int r = i / n, c = i - r * n;
+    dst[r * stride + col + c] = f(src[m0 * n + i + (m0 + r) * gap], r);
+  }
+}
+
 // the virtual cat([x0, x1]) of rows row0 .. row0 + rows - 1: one LDS row per tile row, read coalesced. The
 // caller's barrier follows.
 LSM_HD void load_inputs(const Shape& n, const float* x0, const float* x1, int64_t row0, int rows, float* X, int tid,
                         int nt) {
-  const int SX = n.SX;
-  for (int k = tid; k < rows * n.in0; k += nt) {
-    const int r = k / n.in0, c = k - r * n.in0;
-    X[r * SX + c] = x0[row0 * n.in0 + k];
-  }
-  for (int k = tid; k < rows * n.in1; k += nt) {
-    const int r = k / n.in1, c = k - r * n.in1;
-    X[r * SX + n.in0 + c] = x1[row0 * n.in1 + k];
-  }
+  load_rows(X, n.SX, n.in0, x0, row0, rows, tid, nt);
+  load_rows(X, n.SX, n.in1, x1, row0, rows, tid, nt, 0, AsIs{}, n.in0);
 }
 
 // MLPBase on the lane's staged input row: the feature norm, then fc1 and fc2[i], each Linear, activation,
 // LayerNorm. xrow is overwritten by the feature norm; the result is in cur (nxt is scratch); the last
-// barrier has been passed on return.
-LSM_HD void mlp(const Shape& n, const float* __restrict__ w, float* xrow, float* cur, float* nxt, int wv, int nw) {
+// barrier has been passed on return. The hook sees fc1's input and every layer's activation and LayerNorm
+// output, each behind the barrier that makes the tile's rows whole.
+template <class Hook = NoSaves>
+LSM_HD void mlp(const Shape& n, const float* __restrict__ w, float* xrow, float* cur, float* nxt, int wv, int nw,
+                Hook hook = {}) {
   const int in = n.in, Hd = n.Hd;
   if (n.fnorm) {
     layer_norm(xrow, xrow, in, w + n.o_fn, w + n.o_fn + in, wv, nw);
     LSM_SYNC();
   }
+  hook.rows(SAVED_INPUT, 0);
   for (int k = 0; k <= n.L; ++k) {
     const int din = k == 0 ? in : Hd;
     const float* W = w + n.o_fc[k];
     const float* b = W + Hd * din;
     linear(W, b, Hd, din, k == 0 ? xrow : cur, nxt, wv, nw, n.relu ? 1 : 2);
     LSM_SYNC();
+    hook.rows(SAVED_ACT, k);
     layer_norm(nxt, cur, Hd, b + Hd, b + 2 * Hd, wv, nw);
     LSM_SYNC();
+    hook.rows(SAVED_NORM, k);
   }
 }
 
 // GRU layer l of the lane's row: o[j] = h'_j for this wave's column blocks, from the layer's input x and
 // its state h (both whole LDS rows; h already holds state * mask). No barrier inside: the caller's follows.
+template <class Hook = NoSaves>
 LSM_HD void gru_layer(const Shape& n, const float* __restrict__ w, int l, const float* x, const float* h, float* o,
-                      int wv, int nw) {
+                      int wv, int nw, Hook hook = {}) {
   const int Hd = n.Hd;
   const float* Wih = w + n.o_gru[l];
   const float* Whh = Wih + 3 * Hd * Hd;
@@ -253,6 +332,7 @@ LSM_HD void gru_layer(const Shape& n, const float* __restrict__ w, int l, const 
       const float g = tanhf(fma_(r, hg[jj], ig[jj]));
       const float hp = fma_(z, h[j0 + jj], (1.0f - z) * g);
       o[j0 + jj] = hp;
+      hook.gates(l, j0 + jj, r, z, g, hg[jj]);
     }
   }
 }
@@ -288,9 +368,74 @@ constexpr int pad(int w) { return ((w + 3) & ~3) + 4; }
 
 inline bool in_range(int v, int lo, int hi) { return v >= lo && v <= hi; }
 
-inline bool overlap(const void* a, const void* b, size_t bytes) {
+inline int refuse(const char* prefix, const char* msg) { return lsm_policy_set_error(prefix, msg), 1; }
+
+// the workgroups of a call: one per TILE rows
+inline int64_t tiles_of(int64_t rows) { return (rows + TILE - 1) / TILE; }
+
+// a tile's LDS bytes, from its floats per row
+inline size_t tile_bytes(size_t row_floats) { return (size_t)TILE * row_floats * sizeof(float); }
+
+// whether [a, a + na) and [b, b + nb) share a byte; a null pointer or an empty range shares none
+inline bool overlap(const void* a, size_t na, const void* b, size_t nb) {
+  if (!a || !b || na == 0 || nb == 0) return false;
   const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + bytes && y < x + bytes;
+  return x < y + nb && y < x + na;
+}
+
+// The sizes of a call: T >= 1 steps of C >= 0 rows each, T * C rows within INT32_MAX. c, tc and whole: the
+// unit's words for C, for T * C and for what the caller should split. 0 when fine.
+inline int check_sizes(const char* prefix, const char* c, const char* tc, const char* whole, int64_t C, int32_t T) {
+  char msg[96];
+  if (T < 1) return refuse(prefix, "T < 1");
+  if (C < 0) return snprintf(msg, sizeof msg, "%s < 0", c), refuse(prefix, msg);
+  if (C <= INT32_MAX / (int64_t)T) return 0;
+  return snprintf(msg, sizeof msg, "%s exceeds INT32_MAX rows; split the %s", tc, whole), refuse(prefix, msg);
+}
+
+// The checks of a call's io struct (lsm_head_io, lsm_eval_io, lsm_bwd_io: the same field names) that the units
+// share. Each returns nullptr or the refusal's text; rows: of the call, 0 asks for no input. The fields a
+// config does not read are dropped first, so they are not checked either.
+template <class Io>
+void drop_unread(const Shape& n, Io* f) {
+  if (n.in0 == 0) f->x0 = nullptr;
+  if (n.in1 == 0) f->x1 = nullptr;
+  if (n.RN == 0) f->rnn_states = f->masks = nullptr;
+}
+
+template <class Io>
+const char* inputs_missing(const Shape& n, const Io& f, int64_t rows) {
+  return rows > 0 && ((n.in0 > 0 && !f.x0) || (n.in1 > 0 && !f.x1)) ? "x0 / x1 is null" : nullptr;
+}
+
+template <class Io>
+const char* states_missing(const Shape& n, const Io& f, int64_t rows) {
+  const bool missing = rows > 0 && n.RN > 0 && (!f.rnn_states || !f.masks);
+  return missing ? "the recurrent form needs rnn_states and masks" : nullptr;
+}
+
+inline const char* misaligned(std::initializer_list<const void*> ps, uintptr_t mask = 3,
+                              const char* text = "misaligned pointer") {
+  for (const void* p : ps)
+    if ((uintptr_t)p & mask) return text;
+  return nullptr;
+}
+
+// lsm_head_forward's and lsm_head_evaluate's order of them, after the unit's own drops: the inputs, 4-byte
+// alignment (p4: the unit's own pointers besides the common ones), 8-byte alignment (p8, with the unit's
+// text), the states, rnn_out against rnn_states (rows rows of RN * Hd floats each)
+template <class Io>
+const char* check_io(const Shape& n, const float* weights, const Io& f, int64_t rows,
+                     std::initializer_list<const void*> p4, std::initializer_list<const void*> p8,
+                     const char* p8_text) {
+  const char* why = inputs_missing(n, f, rows);
+  if (!why) why = misaligned({weights, f.x0, f.x1, f.rnn_states, f.masks, f.features, f.rnn_out});
+  if (!why) why = misaligned(p4);
+  if (!why) why = misaligned(p8, 7, p8_text);
+  if (!why) why = states_missing(n, f, rows);
+  const size_t bytes = (size_t)rows * n.RN * n.Hd * sizeof(float);
+  if (!why && overlap(f.rnn_out, bytes, f.rnn_states, bytes)) why = "rnn_out overlaps rnn_states";
+  return why;
 }
 
 // the config's checks and the blob's offsets; returns the blob's length in floats, 0 with a text

@@ -28,11 +28,11 @@
 // multiple of 64 banks (lane r's row starts 4 (r mod 16) banks on for width 64).
 //
 // tile_forward is ONE __host__ __device__ text; lsm_host_head_forward runs it with a tile of one row and
-// one "wave". The per-row pieces (dot4, linear, layer_norm, the GRU cells, the softmax walks) and the
-// config's checks live in lsm_head_tile.h, which the sequence kernel (lsm_evaluate.hip) runs too.
+// one "wave". The kernel's entry, the tile-row copies, the per-row pieces (dot4, linear, layer_norm, MLPBase,
+// the GRU cells, the softmax walks), the config's and the call's checks and launch() live in lsm_head_tile.h,
+// which lsm_evaluate.hip and lsm_backward.hip run too.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
@@ -40,7 +40,7 @@
 #include <vector>
 
 #include "../../include/lsm_policy.h"
-#include "lsm_head_tile.h"   // the per-row pieces, shared with the sequence kernel (lsm_evaluate.hip)
+#include "lsm_head_tile.h"   // the pieces shared with lsm_evaluate.hip and lsm_backward.hip
 
 namespace {
 
@@ -74,35 +74,24 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
 
   // ---- RNNLayer: recurrent_N GRU cells on h = state * mask, then its norm --------------------------------
   for (int l = 0; l < RN; ++l) {
-    for (int k = tid; k < rows * Hd; k += nt) {
-      const int r = k / Hd, c = k - r * Hd;
-      X[r * SX + c] = n.io.rnn_states[((row0 + r) * RN + l) * Hd + c] * n.io.masks[row0 + r];
-    }
+    load_rows(X, SX, Hd, n.io.rnn_states + l * Hd, row0, rows, tid, nt, (RN - 1) * Hd, TimesRow{n.io.masks, row0});
     LSM_SYNC();
     gru_layer(n, w, l, cur + lane * SA, xrow, nxt + lane * SA, wv, nw);
     LSM_SYNC();
-    float* t = cur;
+    float* c = cur;
     cur = nxt;
-    nxt = t;
-    // h'_l of the tile, from LDS: consecutive threads write consecutive floats of a row
-    if (n.io.rnn_out)
-      for (int k = tid; k < rows * Hd; k += nt) {
-        const int r = k / Hd, c = k - r * Hd;
-        n.io.rnn_out[((row0 + r) * RN + l) * Hd + c] = cur[r * SA + c];
-      }
+    nxt = c;
+    // h'_l of the tile, from LDS
+    if (n.io.rnn_out) save_rows(cur, SA, Hd, n.io.rnn_out + l * Hd, row0, rows, tid, nt, (RN - 1) * Hd);
   }
   if (RN > 0) {
     layer_norm(cur + lane * SA, nxt + lane * SA, Hd, w + n.o_rn, w + n.o_rn + Hd, wv, nw);
     LSM_SYNC();
-    float* t = cur;
+    float* c = cur;
     cur = nxt;
-    nxt = t;
+    nxt = c;
   }
-  if (n.io.features)
-    for (int k = tid; k < rows * Hd; k += nt) {
-      const int r = k / Hd, c = k - r * Hd;
-      n.io.features[row0 * Hd + k] = cur[r * SA + c];
-    }
+  if (n.io.features) save_rows(cur, SA, Hd, n.io.features, row0, rows, tid, nt);
 
   // ---- the output layer -------------------------------------------------------------------------------------
   const float* Wo = w + n.o_out;
@@ -131,7 +120,7 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
       if (n.io.bad) *n.io.bad = 1;
       u = u >= 1.0f ? 0.99999994f : 0.0f;   // NaN and negatives: 0
     }
-    const float t = u * s;
+    const float thr = u * s;
     float run = 0.0f;
     int last = -1;
     pick = -1;
@@ -139,7 +128,7 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
       const float e = expf(lg[a] - mx);
       run += e;
       if (e > 0.0f) last = a;
-      if (pick < 0 && run > t) pick = a;
+      if (pick < 0 && run > thr) pick = a;
     }
     if (pick < 0) pick = last < 0 ? 0 : last;
   }
@@ -149,31 +138,19 @@ LSM_HD void tile_forward(const Head& n, const float* __restrict__ w, int64_t row
 }
 
 __global__ __launch_bounds__(BLOCK) void head_kernel(Head n, const float* __restrict__ w) {
-  extern __shared__ float4 lds4[];
-  const int64_t row0 = (int64_t)blockIdx.x * TILE;
-  const int64_t left = n.M - row0;
-  // the wave's index as a scalar: the weight addresses derived from it are then lane-uniform to the compiler
-  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / TILE);
-  tile_forward(n, w, row0, left < TILE ? (int)left : TILE, (int)threadIdx.x & (TILE - 1), wv, WAVES, TILE,
-               reinterpret_cast<float*>(lds4));
+  const Tile t = block_tile(n.M);
+  tile_forward(n, w, t.row0, t.rows, t.lane, t.wv, WAVES, TILE, t.lds);
 }
 
 thread_local char g_err[256];
 
-int fail(const char* msg) {
-  lsm_policy_set_error("head: ", msg);
-  return 1;
-}
+int fail(const char* msg) { return refuse("head: ", msg); }
 
 // the largest tile the limits allow (in = 256, hidden = 128): 134144 bytes, within one workgroup's 160 KB
 constexpr int MAX_TILE_BYTES = TILE * (pad(MAX_IN) + 2 * pad(MAX_HIDDEN)) * (int)sizeof(float);
 static_assert(MAX_TILE_BYTES <= WORKGROUP_LDS_BYTES, "the worst-case tile must fit one workgroup's LDS");
 
-int check_rows(int64_t M) {
-  if (M < 0) return fail("M < 0");
-  if (M > INT32_MAX) return fail("M exceeds INT32_MAX rows; split the batch");
-  return 0;
-}
+int check_rows(int64_t M, int32_t T) { return check_sizes("head: ", "M", "M", "batch", M, T); }
 
 // the tile's LDS floats per row: the input row and two activation rows
 size_t tile_floats(const Shape& n) { return (size_t)n.SX + 2 * (size_t)n.SA; }
@@ -183,12 +160,10 @@ int make_head(const lsm_head_config& c, const float* weights, const lsm_head_io*
   if (layout(c, n, "head: ") == 0) return 1;
   if (!weights) return fail("weights is null");
   if (!io) return fail("io is null");
-  if (check_rows(M)) return 1;
-  // the fields this config does not read or write are dropped first: they are not checked either
+  if (check_rows(M, 1)) return 1;
   lsm_head_io f = *io;
-  if (n->in0 == 0) f.x0 = nullptr;
-  if (n->in1 == 0) f.x1 = nullptr;
-  if (n->RN == 0) f.rnn_states = f.masks = nullptr, f.rnn_out = nullptr;
+  drop_unread(*n, &f);
+  if (n->RN == 0) f.rnn_out = nullptr;
   if (n->kind == LSM_HEAD_ACTOR) {
     f.values = nullptr;
   } else {
@@ -196,17 +171,10 @@ int make_head(const lsm_head_config& c, const float* weights, const lsm_head_io*
     f.actions_i32 = nullptr;
     f.actions_f32 = f.log_probs = f.logits = nullptr;
   }
-  if (M > 0 && ((n->in0 > 0 && !f.x0) || (n->in1 > 0 && !f.x1))) return fail("x0 / x1 is null");
-  const void* p4[] = {weights, f.x0, f.x1, f.rnn_states, f.masks, f.u, f.available_actions, f.actions_i32,
-                      f.actions_f32, f.log_probs, f.logits, f.values, f.features, f.rnn_out};
-  for (const void* p : p4)
-    if ((uintptr_t)p & 3) return fail("misaligned pointer");
-  if ((uintptr_t)f.bad & 7) return fail("misaligned pointer");
-  if (n->RN > 0) {
-    if (M > 0 && (!f.rnn_states || !f.masks)) return fail("the recurrent form needs rnn_states and masks");
-    if (f.rnn_out && M > 0 && overlap(f.rnn_out, f.rnn_states, (size_t)M * n->RN * n->Hd * sizeof(float)))
-      return fail("rnn_out overlaps rnn_states");
-  }
+  const char* why = check_io(*n, weights, f, M,
+                             {f.u, f.available_actions, f.actions_i32, f.actions_f32, f.log_probs, f.logits, f.values},
+                             {f.bad}, "misaligned pointer");
+  if (why) return fail(why);
   if (n->kind == LSM_HEAD_ACTOR && !f.actions_i32 && !f.actions_f32)
     return fail("the actor needs actions_i32 or actions_f32");
   n->w = weights;
@@ -236,9 +204,8 @@ int lsm_head_plan(lsm_head_config cfg, int32_t which, int64_t C, int32_t T, lsm_
   if (which == LSM_HEAD_PLAN_FORWARD) {
     Shape n;
     if (layout(cfg, &n, "head: ") == 0) return 1;
-    if (T < 1) return fail("T < 1");
-    if (C < 0 || C > INT32_MAX / (int64_t)T) return check_rows(C < 0 ? C : (int64_t)INT32_MAX + 1);
-    const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
+    if (check_rows(C, T)) return 1;
+    const size_t lds = tile_bytes(tile_floats(n));
     if (lds > (size_t)MAX_TILE_BYTES) return fail("the tile exceeds the LDS of one workgroup");
     p.SX = n.SX, p.SA = n.SA;
     p.lds_bytes[0] = (int64_t)lds;
@@ -257,13 +224,11 @@ int lsm_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_i
   Head n;
   if (make_head(cfg, weights, io, M, &n)) return 1;
   if (M == 0) return 0;
-  const size_t lds = (size_t)TILE * tile_floats(n) * sizeof(float);
+  const size_t lds = tile_bytes(tile_floats(n));
   if (lds > (size_t)MAX_TILE_BYTES) return fail("the tile exceeds the LDS of one workgroup");
-  const dim3 grid((unsigned)((M + TILE - 1) / TILE)), block(BLOCK);
-  static std::atomic<bool> raised[MAX_DEVICES];   // to the limits' worst case
-  if (const char* why = raise_lds_once(raised, (const void*)head_kernel, MAX_TILE_BYTES)) return fail(why);
-  head_kernel<<<grid, block, lds, (hipStream_t)hip_stream>>>(n, n.w);
-  return hipGetLastError() == hipSuccess ? 0 : fail("launch failed");
+  // the LDS limit: to the limits' worst case
+  const char* why = launch<head_kernel, MAX_TILE_BYTES>((unsigned)tiles_of(M), BLOCK, lds, hip_stream, n, n.w);
+  return why ? fail(why) : 0;
 }
 
 int lsm_host_head_forward(lsm_head_config cfg, const float* weights, const lsm_head_io* io, int64_t M) {

@@ -62,11 +62,22 @@ def test_the_two_kernels_share_one_text(lib):
     assert not {"lsm_evaluate.hip", "lsm_evaluate.h", "lsm_head_tile.h"} & set(deps)
     assert lib.lsm_build_id().decode() == build.build_id()
     shared = open(os.path.join(build.CSRC, "lsm_head_tile.h")).read()
-    for unit in ("lsm_policy.hip", "lsm_evaluate.hip"):
+    for unit in ("lsm_policy.hip", "lsm_evaluate.hip", "lsm_backward.hip"):
         src = open(os.path.join(build.CSRC, unit)).read()
         assert '#include "lsm_head_tile.h"' in src and "lsm_rollout.h" not in src
-        for piece in ("void dot4(", "void linear(", "void layer_norm(", "void gru_layer(", "void masked_softmax("):
+        for piece in ("void dot4(", "void linear(", "void layer_norm(", "void gru_layer(", "void masked_softmax(",
+                      "void save_rows(", "void load_rows(", "void mlp(", "Tile block_tile("):
             assert piece in shared and piece not in src, (unit, piece)
+        # every unit runs the shared MLP, GRU cell and kernel entry, and none writes its own again
+        for call in ("mlp(n, w, ", "gru_layer(n, w, ", "block_tile(n.", "load_inputs(n, "):
+            assert call in src, (unit, call)
+        for text in ("gru_layer_save", "sigmoid_(", "readfirstlane"):
+            assert text not in src, (unit, text)
+    # the one-step kernel and the backward's stage 1 copy their rows through the shared loops; eval_tile and
+    # bwd_tile's gradient stores keep their own (eval_kernel and bwd_kernel are kept byte-identical)
+    for unit in ("lsm_policy.hip", "lsm_backward.hip"):
+        src = open(os.path.join(build.CSRC, unit)).read()
+        assert "load_rows(" in src and "save_rows(" in src, unit
 
 
 def test_scratch_bytes(lib):

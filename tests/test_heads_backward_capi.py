@@ -72,9 +72,20 @@ def test_the_forward_pieces_are_the_shared_ones(lib):
     assert lib.lsm_build_id().decode() == build.build_id()
     src = open(os.path.join(build.CSRC, "lsm_backward.hip")).read()
     assert '#include "lsm_head_tile.h"' in src and "lsm_rollout.h" not in src
-    for piece in ("void dot4(", "void linear(", "void layer_norm(", "void row_sum("):
-        assert piece not in src, piece
-    assert "atomic" not in src.replace("std::atomic<bool> raised", "").replace("#include <atomic>", "")
+    shared = open(os.path.join(build.CSRC, "lsm_head_tile.h")).read()
+    for piece in ("void dot4(", "void linear(", "void layer_norm(", "float row_sum(", "void save_rows(",
+                  "void load_rows(", "void mlp(", "void gru_layer("):
+        assert piece in shared and piece not in src, piece
+    # stage 1 has no MLP or GRU cell of its own: it calls the shared ones with its hook, and copies through the
+    # shared loops
+    stage1 = src.split("// ---- stage 2")[0].split("namespace {")[1]
+    for call in ("mlp(n, w, ", "gru_layer(n, w, ", ", keep);", "load_rows(", "save_rows("):
+        assert call in stage1, call
+    for text in ("linear(", "sigmoid_(", "gru_layer_save"):
+        assert text not in stage1, text
+    assert "ranges_overlap" not in src and "groups_of" not in src
+    # no atomics: the launches' once-per-device flags live in lsm_head_tile.h's launch()
+    assert "atomic" not in src
 
 
 def test_workspace_bytes(lib):
