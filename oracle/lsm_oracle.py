@@ -167,10 +167,61 @@ def _qp(a, b, u_ref, w):
     return np.array([u_ref[k] - lam * (float(a[k]) / w[k]) for k in range(len(a))])
 
 
-class OracleEnv:
-    """One navigation_graph_safe env (training Scenario), reference semantics."""
+MT_BLOCK = 624   # MT19937 state words; numpy's legacy stream regenerates them 624 at a time
 
-    def __init__(self, args, seed, value_table=None, ttr_table=None, integrator="rk45"):
+
+class DrawSource:
+    """A replacement for an OracleEnv's random source (``OracleEnv(..., rng=DrawSource(seed))``).
+
+    ``uniform(lo, hi, size=None)`` answers like ``RandomState(seed).uniform`` (the default source,
+    bit for bit) and keeps, per reset, what the device's staged draw depends on: the 32-bit words
+    drawn (two per double), the stream position the reset started at, and the rejection redraws of
+    randomly_generate_separated_positions (an attempt after the first; ``longest``: the highest attempt
+    index any one loop of the reset reached). ``log[r]`` is the record of
+    the r-th ``reset``. A subclass with another stream overrides ``_doubles`` (n doubles in
+    [0, 1), in draw order) and, if the stream depends on the reset index, ``begin_reset``."""
+
+    def __init__(self, seed):
+        self.seed = int(seed)
+        self._rs = np.random.RandomState(seed)
+        self.words = 0   # words drawn since the seed
+        self.log = []
+
+    def begin_reset(self):
+        self.log.append(dict(start=self.words, words=0, redraws=0, longest=0))
+
+    def note_redraw(self, j):
+        """Attempt j > 0 (counted from 0) of one rejection loop begins."""
+        if self.log:
+            self.log[-1]["redraws"] += 1
+            self.log[-1]["longest"] = max(self.log[-1]["longest"], j)
+
+    def _doubles(self, n):
+        return self._rs.random_sample(n)
+
+    def uniform(self, lo, hi, size=None):
+        n = 1 if size is None else int(np.prod(size))
+        self.words += 2 * n
+        if self.log:
+            self.log[-1]["words"] += 2 * n
+        if type(self)._doubles is DrawSource._doubles:
+            return self._rs.uniform(lo, hi, size)   # numpy's own expression
+        d = self._doubles(n)
+        out = lo + (hi - lo) * d                    # RandomState.uniform: low + (high - low) * double
+        return float(out[0]) if size is None else out.reshape(size)
+
+    @staticmethod
+    def crosses_block(rec):
+        """Whether the reset's draws start inside one 624-word MT19937 block and end in the next."""
+        p0 = rec["start"] % MT_BLOCK
+        return p0 != 0 and p0 + rec["words"] > MT_BLOCK
+
+
+class OracleEnv:
+    """One navigation_graph_safe env (training Scenario), reference semantics. rng: a DrawSource in
+    place of RandomState(seed) (None: RandomState(seed), as the reference seeds numpy)."""
+
+    def __init__(self, args, seed, value_table=None, ttr_table=None, integrator="rk45", rng=None):
         g = (lambda k, d=None: getattr(args, k, d)) if not isinstance(args, dict) else args.get
         self.N = int(g("num_agents"))
         self.L = int(g("num_landmarks"))
@@ -275,7 +326,8 @@ class OracleEnv:
         self.current_time_step = 0
         self.cached_dist_mag = None
         self.edge_list = None
-        self.rng = np.random.RandomState(seed)
+        self.rng = np.random.RandomState(seed) if rng is None else rng
+        self._src = rng   # a DrawSource is told of every reset and rejection redraw
         # episode stats (environment.py:872-926)
         self.prev = dict(travel_time_mean=self.episode_length, travel_distance_mean=0.0,
                          done_percentage=0.0, num_reached_goal_mean=0.0,
@@ -381,6 +433,8 @@ class OracleEnv:
         for i in range(n):
             if i > 0:
                 for j in range(1000):
+                    if j > 0 and self._src is not None:
+                        self._src.note_redraw(j)
                     x = self.rng.uniform(xr[0], xr[1])
                     y = self.rng.uniform(yr[0], yr[1])
                     d = np.min(np.linalg.norm(np.array(positions) - np.array([x, y]), axis=1))
@@ -514,6 +568,8 @@ class OracleEnv:
         self.p_dist[:] = 0.0
         self.atime[:] = 0.0
         self.update_curriculum(num_current_episode)
+        if self._src is not None:
+            self._src.begin_reset()
         if layout is None:
             self.random_scenario()
         else:
@@ -1174,8 +1230,10 @@ class OracleVecEnv:
     """GraphSubprocVecEnv-like batch of OracleEnvs (env k seeded seed + 1000*k)."""
 
     def __init__(self, args, n_envs, seed=0, value_table=None, ttr_table=None, integrator="rk45",
-                 auto_reset=True, seed_offset=0):
-        self.envs = [OracleEnv(args, seed + 1000 * (seed_offset + k), value_table, ttr_table, integrator)
+                 auto_reset=True, seed_offset=0, rng=None):
+        # rng: None, or a callable seed -> DrawSource giving each env its random source
+        self.envs = [OracleEnv(args, seed + 1000 * (seed_offset + k), value_table, ttr_table, integrator,
+                               rng=None if rng is None else rng(seed + 1000 * (seed_offset + k)))
                      for k in range(n_envs)]
         self.auto_reset = auto_reset
 
