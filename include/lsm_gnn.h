@@ -3,7 +3,8 @@
  * (onpolicy/algorithms/utils/gnn.py:545-564): EmbedConv, gnn_layer_N + 1 TransformerConv layers and the
  * readout, for B graphs of E nodes, in one launch. The input is a step's node_obs and its adjacency in
  * either layout; no edge list and no per-edge tensor is built, and nothing synchronises with the host.
- * Inference only (GMPERunner.collect and evaluation, under torch.no_grad()): there is no backward pass.
+ * This is the forward alone (GMPERunner.collect and evaluation, under torch.no_grad()); the backward pass
+ * through the readout and the conv layers is lsm_gnn_backward.h's, which recomputes this forward itself.
  *
  * What is computed (all arithmetic float32). Graph b has nodes x = node_obs[b] [E][F]; the last column is
  * the entity type. Edge (r -> c) exists when the graph's matrix entry [r][c] is nonzero (NaN counts as

@@ -34,7 +34,10 @@ UNITS = {
     # minibatch edge lists from the buffer (include/lsm_minibatch_edges.h, likewise outside build_id())
     "lsm_mb_edges.hip": ["../../include/lsm_minibatch_edges.h"],
     # the fused graph-encoder forward (include/lsm_gnn.h, likewise outside build_id())
-    "lsm_gnn.hip": ["../../include/lsm_gnn.h"],
+    "lsm_gnn.hip": ["../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
+    # the encoder's backward: readout and conv layers (include/lsm_gnn_backward.h, likewise outside build_id());
+    # lsm_gnn_tile.h holds the per-graph forward text the two units share
+    "lsm_gnn_backward.hip": ["../../include/lsm_gnn_backward.h", "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
     # the fused actor / critic heads (include/lsm_policy.h, likewise outside build_id())
     "lsm_policy.hip": ["../../include/lsm_policy.h", "lsm_head_tile.h"],
     # the heads' sequence form (include/lsm_evaluate.h, likewise outside build_id()); lsm_head_tile.h holds

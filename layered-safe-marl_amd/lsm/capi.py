@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
 ``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
-``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h`` and ``include/lsm_backward.h``
-(``liblsm_rollout.so``).
+``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h``, ``include/lsm_backward.h`` and
+``include/lsm_gnn_backward.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -76,6 +76,10 @@ LSM_LOSS_GROUP = 256
 # Every symbol include/lsm_backward.h declares (checked by tests/test_heads_backward_capi.py).
 EXPORTED_BACKWARD = ("lsm_head_backward_workspace_bytes", "lsm_head_backward", "lsm_host_head_backward")
 LSM_BWD_SLAB = 2048
+# Every symbol include/lsm_gnn_backward.h declares (checked by tests/test_gnn_backward_capi.py).
+EXPORTED_GNN_BACKWARD = ("lsm_gnn_backward_workspace_bytes", "lsm_gnn_backward", "lsm_host_gnn_backward",
+                         "lsm_gnn_backward_plan", "lsm_gnn_backward_last_error")
+LSM_GNN_BWD_SLAB = 256
 
 
 class LsmConfig(C.Structure):
@@ -152,6 +156,18 @@ class LsmGnnConfig(C.Structure):
 class LsmGnnLaunchPlan(C.Structure):
     """lsm_gnn_launch_plan (include/lsm_gnn.h): what lsm_gnn_plan fills."""
     _fields_ = [(n, C.c_int32) for n in ("TS", "G", "adj_lds", "fast", "SA", "SK")] + [("lds_bytes", C.c_int64)]
+
+
+class LsmGnnBwdIo(C.Structure):
+    """lsm_gnn_bwd_io (include/lsm_gnn_backward.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("node_obs", "adj", "masks", "agent_id", "dout", "dweights", "dh0",
+                                          "workspace", "bad")]
+
+
+class LsmGnnBwdLaunchPlan(C.Structure):
+    """lsm_gnn_bwd_launch_plan (include/lsm_gnn_backward.h): what lsm_gnn_backward_plan fills."""
+    _fields_ = ([(n, C.c_int32) for n in ("TS", "G", "fast", "adj_lds", "acc_lds", "SA", "SK", "ST")] +
+                [(n, C.c_int64) for n in ("lds_bytes", "slabs", "ws_bytes")])
 
 
 class LsmHeadPlanJob(C.Structure):
@@ -308,6 +324,12 @@ def load_library(path: str = LIB_PATH):
         "lsm_head_backward_workspace_bytes": (SZ, [LsmHeadConfig, I64, I32]),
         "lsm_head_backward": (I32, [LsmHeadConfig, P, C.POINTER(LsmBwdIo), I64, I32, P]),
         "lsm_host_head_backward": (I32, [LsmHeadConfig, P, C.POINTER(LsmBwdIo), I64, I32]),
+        # include/lsm_gnn_backward.h
+        "lsm_gnn_backward_workspace_bytes": (SZ, [LsmGnnConfig, I64, I32]),
+        "lsm_gnn_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32, P]),
+        "lsm_host_gnn_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32]),
+        "lsm_gnn_backward_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnBwdLaunchPlan)]),
+        "lsm_gnn_backward_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

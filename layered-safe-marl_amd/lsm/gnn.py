@@ -5,8 +5,12 @@ one kernel launch on the step's own outputs (``csrc/lsm_gnn.hip`` through ``incl
 ``[B, E, F]`` / ``[B, E, E]``, ``agent_id`` ``[B, 1]`` or ``[B]``) and returns its ``[B, out_dim]`` row per
 graph; ``forward_compact`` reads the compact adjacency layout (one ``[n, E, E]`` table + per-ego
 disconnect words) without expanding it. No edge list, no per-edge tensor and no host synchronisation:
-``process_adj`` is not called. Inference only (``GMPERunner.collect``, evaluation); there is no backward
-pass, and no CPU fallback, as elsewhere in the project.
+``process_adj`` is not called. There is no CPU fallback, as elsewhere in the project.
+
+``GraphEncoder.backward(node_obs, adj, dout, agent_id)`` (``csrc/lsm_gnn_backward.hip`` through
+``include/lsm_gnn_backward.h``) is the backward pass through the readout and the TransformerConv layers: from
+the gradient at ``forward``'s output to the gradient of every conv-layer weight and to ``dh0``, the gradient at
+EmbedConv's output. EmbedConv's own backward is not built yet: its entries of ``dweights`` are 0.
 
 Weights travel as one packed float32 blob (layout: ``include/lsm_gnn.h``). ``pack_weights`` builds it from
 a ``GNNBase`` state dict, checking every shape against the config; ``GraphEncoder.load`` refreshes the
@@ -23,7 +27,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import capi
-from ._device import DeviceOp, OutputCache, _torch, pack_entries, unpack_entries
+from ._device import DeviceOp, OutputCache, _torch, pack_entries, ptr, unpack_entries
 
 AGGR = {"node": capi.LSM_GNN_NODE, "global_mean": capi.LSM_GNN_GLOBAL_MEAN, "global_max": capi.LSM_GNN_GLOBAL_MAX,
         "global_add": capi.LSM_GNN_GLOBAL_ADD}
@@ -137,28 +141,35 @@ class GraphEncoder(DeviceOp):
         super().__init__(device, GnnError, "GraphEncoder", "encoder")
         self._struct = cfg.struct()
         self._out = OutputCache()
+        self._bwd_out = OutputCache()
+        self._last_dweights = None
         self._alloc_weights(weights_floats(cfg), weights)
 
     def load(self, state_dict, prefix: str = "gnn."):
         """Refresh the blob from a GNNBase state dict (after each optimiser step)."""
         self._set(pack_weights(state_dict, self.cfg, prefix))
 
+    def _agent_id(self, agent_id, B):
+        """agent_id as the library reads it ([B] int64, contiguous); None for the global readouts."""
+        torch = _torch()
+        if self.cfg.aggr != "node":
+            return None
+        if agent_id is None:
+            raise GnnError("the 'node' readout needs agent_id")
+        if not isinstance(agent_id, torch.Tensor) or not agent_id.is_cuda:
+            raise GnnError("agent_id must be a CUDA (HIP) tensor; there is no CPU fallback")
+        if agent_id.numel() != B:
+            raise GnnError("agent_id must be [B] or [B, 1], got %s" % (tuple(agent_id.shape),))
+        aid = agent_id.reshape(B)
+        if aid.dtype != torch.int64:
+            aid = aid.long()   # GNNBase.forward: agent_id.long()
+        return aid.contiguous()
+
     def _run(self, node_obs, adj, masks, B, E, N, agent_id, check):
         torch = _torch()
         cfg = self.cfg
         node_obs = self._tensor(node_obs, "node_obs", shape=(B, E, cfg.F))
-        aid = None
-        if cfg.aggr == "node":
-            if agent_id is None:
-                raise GnnError("the 'node' readout needs agent_id")
-            if not isinstance(agent_id, torch.Tensor) or not agent_id.is_cuda:
-                raise GnnError("agent_id must be a CUDA (HIP) tensor; there is no CPU fallback")
-            if agent_id.numel() != B:
-                raise GnnError("agent_id must be [B] or [B, 1], got %s" % (tuple(agent_id.shape),))
-            aid = agent_id.reshape(B)
-            if aid.dtype != torch.int64:
-                aid = aid.long()   # GNNBase.forward: agent_id.long()
-            aid = aid.contiguous()
+        aid = self._agent_id(agent_id, B)
         sh = self._stream()
         out = self._out.get((B, sh), lambda: torch.empty((B, cfg.out_dim), dtype=torch.float32, device=self.device))
         rc = self.lib.lsm_gnn_forward(self._struct, C.c_void_p(self.weights.data_ptr()),
@@ -207,3 +218,87 @@ class GraphEncoder(DeviceOp):
         return self.forward_compact(node, adj, adj_mask, num_agents, aid, check=check)
 
     __call__ = forward
+
+    # ---- the backward pass: readout and conv layers (include/lsm_gnn_backward.h) ---------------------------------
+
+    def _bwd_outputs(self, B, E):
+        torch = _torch()
+        n = int(self.lib.lsm_gnn_backward_workspace_bytes(self._struct, B, E))
+        if n == 0 and B > 0:
+            raise GnnError(self.lib.lsm_gnn_backward_last_error().decode())
+        f32 = dict(dtype=torch.float32, device=self.device)
+        return {"dweights": torch.zeros(self._n, **f32), "dh0": torch.empty((B, E, self.cfg.embed_hidden), **f32),
+                "workspace": torch.empty(max(n // 8, 1), dtype=torch.float64, device=self.device)}
+
+    def _run_backward(self, node_obs, adj, masks, B, E, N, dout, agent_id, dh0, check):
+        cfg = self.cfg
+        node_obs = self._tensor(node_obs, "node_obs", shape=(B, E, cfg.F))
+        dout = self._tensor(dout, "dout", shape=(B, cfg.out_dim), detach=True)
+        aid = self._agent_id(agent_id, B)
+        sh = self._stream()
+        out = self._bwd_out.get((B, E, sh), lambda: self._bwd_outputs(B, E))
+        io = capi.LsmGnnBwdIo(node_obs=ptr(node_obs), adj=ptr(adj), masks=ptr(masks), agent_id=ptr(aid), dout=ptr(dout),
+                              dweights=ptr(out["dweights"]), dh0=ptr(out["dh0"]) if dh0 else None,
+                              workspace=ptr(out["workspace"]), bad=ptr(self.bad))
+        rc = self.lib.lsm_gnn_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
+                                       C.c_void_p(sh))
+        self._finish(rc, self.lib.lsm_gnn_backward_last_error, check,
+                     "an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the encoder")
+        self._last_dweights = out["dweights"]
+        return {"dweights": out["dweights"], "dh0": out["dh0"] if dh0 else None}
+
+    def backward(self, node_obs, adj, dout, agent_id=None, dh0: bool = False, check: bool = False):
+        """The backward pass through the readout and the conv layers on forward's inputs: dout [B, out_dim] is
+        the gradient at forward's output (PolicyHead.backward's dx1). Two launches, no host synchronisation; the
+        call recomputes the forward itself. Returns preallocated device tensors, cached per (B, E, stream) and
+        valid until the next call with them: dweights [floats of the blob] -- the gradient of every conv-layer
+        weight in the blob's own layout, overwritten, not accumulated, 0 over EmbedConv's entries (gradients()
+        names them) -- and, with dh0=True, dh0 [B, E, embed_hidden], the gradient at EmbedConv's output (None
+        otherwise). The workspace (one float64 row of the conv entries per 256 graphs) is cached with them."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        adj = self._tensor(adj, "adj", shape=(B, E, E))
+        return self._run_backward(node_obs, adj, None, B, E, 1, dout, agent_id, dh0, check)
+
+    def backward_compact(self, node_obs, table, masks, num_agents: int, dout, agent_id=None, dh0: bool = False,
+                         check: bool = False):
+        """backward on forward_compact's inputs."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        N = int(num_agents)
+        if N < 1 or B % N:
+            raise GnnError("node_obs holds %d graphs, not a multiple of num_agents = %d" % (B, N))
+        table = self._tensor(table, "table", shape=(B // N, E, E))
+        if not isinstance(masks, torch.Tensor) or masks.numel() != B * ((E + 63) // 64):
+            raise GnnError("masks must hold [n * N, ceil(E / 64)] words")
+        masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", dtype=torch.int64, shape=(B, (E + 63) // 64))
+        return self._run_backward(node_obs, table, masks, B, E, N, dout, agent_id, dh0, check)
+
+    def backward_step(self, node_obs, adj, adj_mask, num_agents: int, dout, agent_id=None, dh0: bool = False,
+                      check: bool = False):
+        """backward on forward_step's inputs (either adjacency layout); dout [n * N, out_dim]."""
+        E, F = int(node_obs.shape[-2]), int(node_obs.shape[-1])
+        node = node_obs.reshape(-1, E, F)
+        aid = None if agent_id is None else agent_id.reshape(-1)
+        if adj_mask is None:
+            return self.backward(node, adj.reshape(-1, E, E), dout, aid, dh0=dh0, check=check)
+        return self.backward_compact(node, adj, adj_mask, num_agents, dout, aid, dh0=dh0, check=check)
+
+    def gradients(self, prefix: str = "gnn."):
+        """{state-dict name: gradient}: views, without a copy, of the last backward()'s dweights in the
+        parameters' shapes, under the names of weight_entries (layer_norm entries only with layer norm; the
+        EmbedConv entries are 0 until its backward exists). They are that call's cached tensor: valid until the
+        next backward() with its (B, E, stream)."""
+        if self._last_dweights is None:
+            raise GnnError("gradients() follows a backward()")
+        out, o = {}, 0
+        for name, shape in weight_entries(self.cfg):
+            n = int(np.prod(shape))
+            if self.cfg.layer_norm or ".layer_norm." not in name:
+                out[prefix + name] = self._last_dweights[o:o + n].view(shape)
+            o += n
+        return out

@@ -582,3 +582,28 @@ class DevicePolicy:
         out["critic"] = self.critic_head.backward(x0, x1, mb.get("rnn_states_critic"), mb.get("masks"), T,
                                                   dvalues=loss_out["dvalues"], dx=dx)
         return out
+
+    def encoders_backward(self, mb, heads_out, update_actor: bool = True, dh0: bool = False):
+        """The encoders' half, after heads_backward(..., dx=True) on the same minibatch: GraphEncoder.backward of
+        both encoders on mb['node_obs'], mb['adj'], mb['agent_id'] from each head's dx1, the gradient at the
+        encoder's output. update_actor=False: the critic's encoder alone. Two encoder calls, four launches, no
+        host synchronisation. Returns {'actor': ..., 'critic': ...}, each GraphEncoder.backward's dict ('actor'
+        None without update_actor); every conv-layer weight's gradient is then in actor_encoder.gradients() /
+        critic_encoder.gradients(), and with dh0=True each dict's dh0 is the seed of EmbedConv's backward, which
+        is not built yet."""
+        if self.last_head_inputs is None:
+            raise PolicyError("heads_backward follows ppo_loss or evaluate_actions on the same minibatch")
+        if self.actor_encoder is self.critic_encoder:
+            raise PolicyError("heads_backward needs two encoder objects: a shared one's cached output holds the "
+                              "critic's features by now, and the actor would be differentiated at them")
+        if mb.get("adj") is None:
+            raise PolicyError("the minibatch has no dense adj (edges=True): the encoder reads the [B, E, E] matrix")
+        out = {"actor": None}
+        for who, enc in (("actor", self.actor_encoder), ("critic", self.critic_encoder)):
+            if who == "actor" and not update_actor:
+                continue
+            h = heads_out.get(who)
+            if h is None or h.get("dx1") is None:
+                raise PolicyError("heads_out has no %s dx1: call heads_backward(..., dx=True)" % who)
+            out[who] = enc.backward(mb["node_obs"], mb["adj"], h["dx1"], mb["agent_id"], dh0=dh0)
+        return out
