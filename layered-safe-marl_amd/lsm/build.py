@@ -38,6 +38,9 @@ UNITS = {
     # the encoder's backward: readout and conv layers (include/lsm_gnn_backward.h, likewise outside build_id());
     # lsm_gnn_tile.h holds the per-graph forward text the two units share
     "lsm_gnn_backward.hip": ["../../include/lsm_gnn_backward.h", "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
+    # EmbedConv's backward, from dh0 (include/lsm_gnn_embed_backward.h, likewise outside build_id())
+    "lsm_gnn_embed_backward.hip": ["../../include/lsm_gnn_embed_backward.h", "../../include/lsm_gnn_backward.h",
+                                   "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
     # the fused actor / critic heads (include/lsm_policy.h, likewise outside build_id())
     "lsm_policy.hip": ["../../include/lsm_policy.h", "lsm_head_tile.h"],
     # the heads' sequence form (include/lsm_evaluate.h, likewise outside build_id()); lsm_head_tile.h holds

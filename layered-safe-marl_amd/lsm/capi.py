@@ -80,6 +80,11 @@ LSM_BWD_SLAB = 2048
 EXPORTED_GNN_BACKWARD = ("lsm_gnn_backward_workspace_bytes", "lsm_gnn_backward", "lsm_host_gnn_backward",
                          "lsm_gnn_backward_plan", "lsm_gnn_backward_last_error")
 LSM_GNN_BWD_SLAB = 256
+# Every symbol include/lsm_gnn_embed_backward.h declares (checked by tests/test_gnn_embed_backward_capi.py); its
+# slabs are LSM_GNN_BWD_SLAB graphs.
+EXPORTED_GNN_EMBED_BACKWARD = ("lsm_gnn_embed_floats", "lsm_gnn_embed_backward_workspace_bytes",
+                               "lsm_gnn_embed_backward", "lsm_host_gnn_embed_backward",
+                               "lsm_gnn_embed_backward_plan", "lsm_gnn_embed_backward_last_error")
 
 
 class LsmConfig(C.Structure):
@@ -167,6 +172,17 @@ class LsmGnnBwdIo(C.Structure):
 class LsmGnnBwdLaunchPlan(C.Structure):
     """lsm_gnn_bwd_launch_plan (include/lsm_gnn_backward.h): what lsm_gnn_backward_plan fills."""
     _fields_ = ([(n, C.c_int32) for n in ("TS", "G", "fast", "adj_lds", "acc_lds", "SA", "SK", "ST")] +
+                [(n, C.c_int64) for n in ("lds_bytes", "slabs", "ws_bytes")])
+
+
+class LsmGnnEmbedBwdIo(C.Structure):
+    """lsm_gnn_embed_bwd_io (include/lsm_gnn_embed_backward.h): one call's tensors, passed by pointer."""
+    _fields_ = [(n, C.c_void_p) for n in ("node_obs", "adj", "masks", "dh0", "dembed", "workspace", "bad")]
+
+
+class LsmGnnEmbedBwdLaunchPlan(C.Structure):
+    """lsm_gnn_embed_bwd_launch_plan (include/lsm_gnn_embed_backward.h): what lsm_gnn_embed_backward_plan fills."""
+    _fields_ = ([(n, C.c_int32) for n in ("TS", "G", "fast", "adj_lds", "acc_lds", "S", "per_graph", "entries")] +
                 [(n, C.c_int64) for n in ("lds_bytes", "slabs", "ws_bytes")])
 
 
@@ -330,6 +346,13 @@ def load_library(path: str = LIB_PATH):
         "lsm_host_gnn_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32]),
         "lsm_gnn_backward_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnBwdLaunchPlan)]),
         "lsm_gnn_backward_last_error": (C.c_char_p, []),
+        # include/lsm_gnn_embed_backward.h (its slabs are LSM_GNN_BWD_SLAB graphs)
+        "lsm_gnn_embed_floats": (SZ, [LsmGnnConfig]),
+        "lsm_gnn_embed_backward_workspace_bytes": (SZ, [LsmGnnConfig, I64, I32]),
+        "lsm_gnn_embed_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnEmbedBwdIo), I64, I32, I32, P]),
+        "lsm_host_gnn_embed_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnEmbedBwdIo), I64, I32, I32]),
+        "lsm_gnn_embed_backward_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnEmbedBwdLaunchPlan)]),
+        "lsm_gnn_embed_backward_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -10,7 +10,9 @@ disconnect words) without expanding it. No edge list, no per-edge tensor and no 
 ``GraphEncoder.backward(node_obs, adj, dout, agent_id)`` (``csrc/lsm_gnn_backward.hip`` through
 ``include/lsm_gnn_backward.h``) is the backward pass through the readout and the TransformerConv layers: from
 the gradient at ``forward``'s output to the gradient of every conv-layer weight and to ``dh0``, the gradient at
-EmbedConv's output. EmbedConv's own backward is not built yet: its entries of ``dweights`` are 0.
+EmbedConv's output. ``GraphEncoder.embed_backward(node_obs, adj, dh0)`` (``csrc/lsm_gnn_embed_backward.hip`` through
+``include/lsm_gnn_embed_backward.h``) is EmbedConv's own backward, from ``dh0`` to the gradient of the blob's
+EmbedConv entries; ``backward(..., embed=True)`` runs both and leaves a complete gradient in ``dweights``.
 
 Weights travel as one packed float32 blob (layout: ``include/lsm_gnn.h``). ``pack_weights`` builds it from
 a ``GNNBase`` state dict, checking every shape against the config; ``GraphEncoder.load`` refreshes the
@@ -142,6 +144,7 @@ class GraphEncoder(DeviceOp):
         self._struct = cfg.struct()
         self._out = OutputCache()
         self._bwd_out = OutputCache()
+        self._emb_out = OutputCache()
         self._last_dweights = None
         self._alloc_weights(weights_floats(cfg), weights)
 
@@ -230,7 +233,7 @@ class GraphEncoder(DeviceOp):
         return {"dweights": torch.zeros(self._n, **f32), "dh0": torch.empty((B, E, self.cfg.embed_hidden), **f32),
                 "workspace": torch.empty(max(n // 8, 1), dtype=torch.float64, device=self.device)}
 
-    def _run_backward(self, node_obs, adj, masks, B, E, N, dout, agent_id, dh0, check):
+    def _run_backward(self, node_obs, adj, masks, B, E, N, dout, agent_id, dh0, check, embed=False):
         cfg = self.cfg
         node_obs = self._tensor(node_obs, "node_obs", shape=(B, E, cfg.F))
         dout = self._tensor(dout, "dout", shape=(B, cfg.out_dim), detach=True)
@@ -238,32 +241,38 @@ class GraphEncoder(DeviceOp):
         sh = self._stream()
         out = self._bwd_out.get((B, E, sh), lambda: self._bwd_outputs(B, E))
         io = capi.LsmGnnBwdIo(node_obs=ptr(node_obs), adj=ptr(adj), masks=ptr(masks), agent_id=ptr(aid), dout=ptr(dout),
-                              dweights=ptr(out["dweights"]), dh0=ptr(out["dh0"]) if dh0 else None,
+                              dweights=ptr(out["dweights"]), dh0=ptr(out["dh0"]) if dh0 or embed else None,
                               workspace=ptr(out["workspace"]), bad=ptr(self.bad))
         rc = self.lib.lsm_gnn_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
                                        C.c_void_p(sh))
         self._finish(rc, self.lib.lsm_gnn_backward_last_error, check,
                      "an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the encoder")
         self._last_dweights = out["dweights"]
+        if embed:   # the same stream: seeded by this call's dh0, into the EmbedConv range of the same dweights
+            self._run_embed_backward(node_obs, adj, masks, B, E, N, out["dh0"], out["dweights"], check)
         return {"dweights": out["dweights"], "dh0": out["dh0"] if dh0 else None}
 
-    def backward(self, node_obs, adj, dout, agent_id=None, dh0: bool = False, check: bool = False):
+    def backward(self, node_obs, adj, dout, agent_id=None, dh0: bool = False, check: bool = False,
+                 embed: bool = False):
         """The backward pass through the readout and the conv layers on forward's inputs: dout [B, out_dim] is
         the gradient at forward's output (PolicyHead.backward's dx1). Two launches, no host synchronisation; the
         call recomputes the forward itself. Returns preallocated device tensors, cached per (B, E, stream) and
         valid until the next call with them: dweights [floats of the blob] -- the gradient of every conv-layer
         weight in the blob's own layout, overwritten, not accumulated, 0 over EmbedConv's entries (gradients()
         names them) -- and, with dh0=True, dh0 [B, E, embed_hidden], the gradient at EmbedConv's output (None
-        otherwise). The workspace (one float64 row of the conv entries per 256 graphs) is cached with them."""
+        otherwise). The workspace (one float64 row of the conv entries per 256 graphs) is cached with them.
+        embed=True: EmbedConv's backward (embed_backward) follows on the same stream, two more launches, seeded
+        by this call's dh0 (produced internally whatever dh0= says) and writing the EmbedConv range of the same
+        dweights, which is then the complete gradient. embed=False: the EmbedConv range is 0."""
         torch = _torch()
         if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
             raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
         B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
         adj = self._tensor(adj, "adj", shape=(B, E, E))
-        return self._run_backward(node_obs, adj, None, B, E, 1, dout, agent_id, dh0, check)
+        return self._run_backward(node_obs, adj, None, B, E, 1, dout, agent_id, dh0, check, embed)
 
     def backward_compact(self, node_obs, table, masks, num_agents: int, dout, agent_id=None, dh0: bool = False,
-                         check: bool = False):
+                         check: bool = False, embed: bool = False):
         """backward on forward_compact's inputs."""
         torch = _torch()
         if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
@@ -276,23 +285,97 @@ class GraphEncoder(DeviceOp):
         if not isinstance(masks, torch.Tensor) or masks.numel() != B * ((E + 63) // 64):
             raise GnnError("masks must hold [n * N, ceil(E / 64)] words")
         masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", dtype=torch.int64, shape=(B, (E + 63) // 64))
-        return self._run_backward(node_obs, table, masks, B, E, N, dout, agent_id, dh0, check)
+        return self._run_backward(node_obs, table, masks, B, E, N, dout, agent_id, dh0, check, embed)
 
     def backward_step(self, node_obs, adj, adj_mask, num_agents: int, dout, agent_id=None, dh0: bool = False,
-                      check: bool = False):
+                      check: bool = False, embed: bool = False):
         """backward on forward_step's inputs (either adjacency layout); dout [n * N, out_dim]."""
         E, F = int(node_obs.shape[-2]), int(node_obs.shape[-1])
         node = node_obs.reshape(-1, E, F)
         aid = None if agent_id is None else agent_id.reshape(-1)
         if adj_mask is None:
-            return self.backward(node, adj.reshape(-1, E, E), dout, aid, dh0=dh0, check=check)
-        return self.backward_compact(node, adj, adj_mask, num_agents, dout, aid, dh0=dh0, check=check)
+            return self.backward(node, adj.reshape(-1, E, E), dout, aid, dh0=dh0, check=check, embed=embed)
+        return self.backward_compact(node, adj, adj_mask, num_agents, dout, aid, dh0=dh0, check=check, embed=embed)
+
+    # ---- EmbedConv's backward, from dh0 (include/lsm_gnn_embed_backward.h) ---------------------------------------
+
+    def embed_floats(self) -> int:
+        """lsm_gnn_embed_floats(cfg): the blob's EmbedConv entries, [0, offset of conv layer 0)."""
+        return int(self.lib.lsm_gnn_embed_floats(self._struct))
+
+    def _emb_outputs(self, B, E):
+        torch = _torch()
+        n = int(self.lib.lsm_gnn_embed_backward_workspace_bytes(self._struct, B, E))
+        if n == 0 and B > 0:
+            raise GnnError(self.lib.lsm_gnn_embed_backward_last_error().decode())
+        return {"dembed": torch.zeros(self.embed_floats(), dtype=torch.float32, device=self.device),
+                "workspace": torch.empty(max(n // 8, 1), dtype=torch.float64, device=self.device)}
+
+    def _run_embed_backward(self, node_obs, adj, masks, B, E, N, dh0, out, check):
+        torch = _torch()
+        cfg = self.cfg
+        node_obs = self._tensor(node_obs, "node_obs", shape=(B, E, cfg.F))
+        dh0 = self._tensor(dh0, "dh0", shape=(B, E, cfg.embed_hidden), detach=True)
+        sh = self._stream()
+        cached = self._emb_out.get((B, E, sh), lambda: self._emb_outputs(B, E))
+        n = self.embed_floats()
+        if out is None:
+            out = cached["dembed"]
+        elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.float32
+              or not out.is_contiguous() or out.numel() < n):
+            raise GnnError("out must be a contiguous float32 CUDA (HIP) tensor of at least %d values" % n)
+        io = capi.LsmGnnEmbedBwdIo(node_obs=ptr(node_obs), adj=ptr(adj), masks=ptr(masks), dh0=ptr(dh0),
+                                   dembed=ptr(out), workspace=ptr(cached["workspace"]), bad=ptr(self.bad))
+        rc = self.lib.lsm_gnn_embed_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
+                                             C.c_void_p(sh))
+        self._finish(rc, self.lib.lsm_gnn_embed_backward_last_error, check,
+                     "an entity type outside [0, num_embeddings) reached the encoder")
+        return {"dembed": out.reshape(-1)[:n]}
+
+    def embed_backward(self, node_obs, adj, dh0, out=None, check: bool = False):
+        """EmbedConv's backward on forward's inputs: dh0 [B, E, embed_hidden] is the gradient at EmbedConv's
+        output (backward's dh0). Two launches, no host synchronisation; the per-edge MLP is recomputed. Returns
+        {'dembed': tensor}: the gradient of the blob's EmbedConv entries (entity embedding, lin1, the shared
+        LayerNorm, the embed layers) in the blob's own layout, [embed_floats()] values, overwritten, not
+        accumulated; preallocated and cached per (B, E, stream) with the workspace, valid until the next call
+        with them. out=: a contiguous float32 device tensor to write into instead (its first embed_floats()
+        values; a backward()'s dweights, for one)."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        adj = self._tensor(adj, "adj", shape=(B, E, E))
+        return self._run_embed_backward(node_obs, adj, None, B, E, 1, dh0, out, check)
+
+    def embed_backward_compact(self, node_obs, table, masks, num_agents: int, dh0, out=None, check: bool = False):
+        """embed_backward on forward_compact's inputs."""
+        torch = _torch()
+        if not isinstance(node_obs, torch.Tensor) or node_obs.dim() != 3:
+            raise GnnError("node_obs must be a CUDA (HIP) tensor [B, E, F]; there is no CPU fallback")
+        B, E = int(node_obs.shape[0]), int(node_obs.shape[1])
+        N = int(num_agents)
+        if N < 1 or B % N:
+            raise GnnError("node_obs holds %d graphs, not a multiple of num_agents = %d" % (B, N))
+        table = self._tensor(table, "table", shape=(B // N, E, E))
+        if not isinstance(masks, torch.Tensor) or masks.numel() != B * ((E + 63) // 64):
+            raise GnnError("masks must hold [n * N, ceil(E / 64)] words")
+        masks = self._tensor(masks.reshape(B, (E + 63) // 64), "masks", dtype=torch.int64, shape=(B, (E + 63) // 64))
+        return self._run_embed_backward(node_obs, table, masks, B, E, N, dh0, out, check)
+
+    def embed_backward_step(self, node_obs, adj, adj_mask, num_agents: int, dh0, out=None, check: bool = False):
+        """embed_backward on forward_step's inputs (either adjacency layout); dh0 [n * N, E, embed_hidden]."""
+        E, F = int(node_obs.shape[-2]), int(node_obs.shape[-1])
+        node = node_obs.reshape(-1, E, F)
+        dh0 = dh0.reshape(-1, E, self.cfg.embed_hidden)
+        if adj_mask is None:
+            return self.embed_backward(node, adj.reshape(-1, E, E), dh0, out=out, check=check)
+        return self.embed_backward_compact(node, adj, adj_mask, num_agents, dh0, out=out, check=check)
 
     def gradients(self, prefix: str = "gnn."):
         """{state-dict name: gradient}: views, without a copy, of the last backward()'s dweights in the
-        parameters' shapes, under the names of weight_entries (layer_norm entries only with layer norm; the
-        EmbedConv entries are 0 until its backward exists). They are that call's cached tensor: valid until the
-        next backward() with its (B, E, stream)."""
+        parameters' shapes, under the names of weight_entries (layer_norm entries only with layer norm). After
+        backward(embed=True) this is the complete gradient; after a plain backward() the EmbedConv entries are 0.
+        They are that call's cached tensor: valid until the next backward() with its (B, E, stream)."""
         if self._last_dweights is None:
             raise GnnError("gradients() follows a backward()")
         out, o = {}, 0

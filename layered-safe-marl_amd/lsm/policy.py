@@ -583,14 +583,16 @@ class DevicePolicy:
                                                   dvalues=loss_out["dvalues"], dx=dx)
         return out
 
-    def encoders_backward(self, mb, heads_out, update_actor: bool = True, dh0: bool = False):
+    def encoders_backward(self, mb, heads_out, update_actor: bool = True, dh0: bool = False, embed: bool = False):
         """The encoders' half, after heads_backward(..., dx=True) on the same minibatch: GraphEncoder.backward of
         both encoders on mb['node_obs'], mb['adj'], mb['agent_id'] from each head's dx1, the gradient at the
         encoder's output. update_actor=False: the critic's encoder alone. Two encoder calls, four launches, no
         host synchronisation. Returns {'actor': ..., 'critic': ...}, each GraphEncoder.backward's dict ('actor'
         None without update_actor); every conv-layer weight's gradient is then in actor_encoder.gradients() /
-        critic_encoder.gradients(), and with dh0=True each dict's dh0 is the seed of EmbedConv's backward, which
-        is not built yet."""
+        critic_encoder.gradients(), and with dh0=True each dict's dh0 is the gradient at EmbedConv's output.
+        embed=True: GraphEncoder.embed_backward follows each call on the same stream, seeded by that dh0 (two more
+        launches per encoder), and gradients() then names every encoder weight's gradient, EmbedConv's included;
+        by default the EmbedConv entries are 0, as before."""
         if self.last_head_inputs is None:
             raise PolicyError("heads_backward follows ppo_loss or evaluate_actions on the same minibatch")
         if self.actor_encoder is self.critic_encoder:
@@ -605,5 +607,5 @@ class DevicePolicy:
             h = heads_out.get(who)
             if h is None or h.get("dx1") is None:
                 raise PolicyError("heads_out has no %s dx1: call heads_backward(..., dx=True)" % who)
-            out[who] = enc.backward(mb["node_obs"], mb["adj"], h["dx1"], mb["agent_id"], dh0=dh0)
+            out[who] = enc.backward(mb["node_obs"], mb["adj"], h["dx1"], mb["agent_id"], dh0=dh0, embed=embed)
         return out
