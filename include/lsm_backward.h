@@ -4,8 +4,8 @@
  * at the head's two input blocks (dx1 is the seed of the encoder's backward), on a time-major minibatch of C
  * chunks of T steps, as lsm_evaluate.h takes it. What the reference reaches with loss.backward() through
  * ACTLayer / v_out, RNNLayer (BPTT through the GRU) and MLPBase. The weight blob, lsm_head_config and its
- * limits are lsm_policy.h's. Discrete action spaces only. The encoder's backward, the gradient norm and the
- * optimiser are not here.
+ * limits are lsm_policy.h's. Discrete action spaces only. The encoder's backward is not here; the gradient norm,
+ * the clipping and the optimiser are lsm_optim.h's, on dweights as this call leaves it.
  *
  * The call is self-contained: it recomputes the forward of lsm_evaluate.h's steps 1-3 (and the NaN rule of
  * step 4) from the same inputs with the same per-row arithmetic (csrc/lsm_head_tile.h), so the gradient is

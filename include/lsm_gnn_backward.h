@@ -5,7 +5,7 @@
  * config, the weight blob, the two adjacency layouts and the forward's formulas are lsm_gnn.h's. EmbedConv's
  * own backward is NOT here: the blob's EmbedConv entries, [0, offset of conv layer 0's query weight), are
  * written as 0 in this version; their gradient follows from dh0 (a sum over the edges of a per-edge MLP) and is
- * the next piece. The gradient norm and the optimiser are not here either.
+ * the next piece. The gradient norm and the optimiser are lsm_optim.h's.
  *
  * The call is self-contained: it recomputes the forward from the same inputs with the forward's own per-graph
  * text (csrc/lsm_gnn_tile.h), so the gradient is that of the function lsm_gnn_forward computes. No edge list and

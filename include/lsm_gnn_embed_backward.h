@@ -4,7 +4,7 @@
  * the shared LayerNorm and the embed layers, [0, lsm_gnn_embed_floats(cfg)) of the packed blob, in the blob's
  * own layout and order. The config, the blob, the two adjacency layouts, the edge set, the attribute e, the
  * disconnect bits and the entity-type rule are lsm_gnn.h's. The call needs (weights, node_obs, adj, dh0) only: it
- * does not run the conv layers. The gradient norm, the clipping and the optimiser are not here.
+ * does not run the conv layers. The gradient norm, the clipping and the optimiser are lsm_optim.h's.
  *
  * All arithmetic float32 unless stated. Per graph, with E nodes, Hd = embed_hidden, EL = embed_layer_N,
  * K = F - 1 + embedding_size + 1, x_r node r's features, t_r = trunc(x_r[F-1]) its entity type, emb the entity

@@ -50,6 +50,8 @@ UNITS = {
     "lsm_loss.hip": ["../../include/lsm_loss.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
     # the heads' backward pass (include/lsm_backward.h, likewise outside build_id())
     "lsm_backward.hip": ["../../include/lsm_backward.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
+    # the gradient norm, the clipping and Adam on the blobs (include/lsm_optim.h, likewise outside build_id())
+    "lsm_optim.hip": ["../../include/lsm_optim.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
 ``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
-``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h``, ``include/lsm_backward.h`` and
-``include/lsm_gnn_backward.h`` (``liblsm_rollout.so``).
+``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h``, ``include/lsm_backward.h``,
+``include/lsm_gnn_backward.h``, ``include/lsm_gnn_embed_backward.h`` and ``include/lsm_optim.h``
+(``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -85,6 +86,9 @@ LSM_GNN_BWD_SLAB = 256
 EXPORTED_GNN_EMBED_BACKWARD = ("lsm_gnn_embed_floats", "lsm_gnn_embed_backward_workspace_bytes",
                                "lsm_gnn_embed_backward", "lsm_host_gnn_embed_backward",
                                "lsm_gnn_embed_backward_plan", "lsm_gnn_embed_backward_last_error")
+# Every symbol include/lsm_optim.h declares (checked by tests/test_optim_capi.py).
+EXPORTED_OPTIM = ("lsm_optim_workspace_bytes", "lsm_optim_step", "lsm_host_optim_step", "lsm_optim_last_error")
+LSM_OPT_MAX_GROUPS, LSM_OPT_MAX_SEGMENTS, LSM_OPT_CHUNK, LSM_OPT_LANES = 4, 8, 1024, 256
 
 
 class LsmConfig(C.Structure):
@@ -239,6 +243,19 @@ class LsmBwdIo(C.Structure):
                                           "dvalues", "dweights", "dx0", "dx1", "workspace")]
 
 
+class LsmOptimSegment(C.Structure):
+    """lsm_optim_segment (include/lsm_optim.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("weights", "grads", "exp_avg", "exp_avg_sq")] + [("n", C.c_int64)]
+
+
+class LsmOptimGroup(C.Structure):
+    """lsm_optim_group (include/lsm_optim.h): one parameter group of a call's table."""
+    _fields_ = ([("segments", LsmOptimSegment * LSM_OPT_MAX_SEGMENTS)] +
+                [(n, C.c_int32) for n in ("n_segments", "use_max_grad_norm", "skip_nonfinite", "reserved")] +
+                [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "max_grad_norm")] +
+                [("state", C.c_void_p), ("info", C.c_void_p)])
+
+
 class LsmError(RuntimeError):
     pass
 
@@ -353,6 +370,11 @@ def load_library(path: str = LIB_PATH):
         "lsm_host_gnn_embed_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnEmbedBwdIo), I64, I32, I32]),
         "lsm_gnn_embed_backward_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnEmbedBwdLaunchPlan)]),
         "lsm_gnn_embed_backward_last_error": (C.c_char_p, []),
+        # include/lsm_optim.h
+        "lsm_optim_workspace_bytes": (SZ, [C.POINTER(LsmOptimGroup), I32]),
+        "lsm_optim_step": (I32, [C.POINTER(LsmOptimGroup), I32, P, P]),
+        "lsm_host_optim_step": (I32, [C.POINTER(LsmOptimGroup), I32, P]),
+        "lsm_optim_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

@@ -146,11 +146,18 @@ class GraphEncoder(DeviceOp):
         self._bwd_out = OutputCache()
         self._emb_out = OutputCache()
         self._last_dweights = None
+        self._last_embed = False   # whether the last backward() ran with embed=True (lsm.optim.DeviceAdam asks)
         self._alloc_weights(weights_floats(cfg), weights)
 
     def load(self, state_dict, prefix: str = "gnn."):
         """Refresh the blob from a GNNBase state dict (after each optimiser step)."""
         self._set(pack_weights(state_dict, self.cfg, prefix))
+
+    def state_dict(self, prefix: str = "gnn."):
+        """The current device blob as {name: float32 tensor}, the inverse of load (unpack_weights; one
+        download): a checkpoint after lsm.optim.DeviceAdam's steps needs no torch module."""
+        torch = _torch()
+        return {k: torch.from_numpy(v) for k, v in unpack_weights(self.weights.cpu().numpy(), self.cfg, prefix).items()}
 
     def _agent_id(self, agent_id, B):
         """agent_id as the library reads it ([B] int64, contiguous); None for the global readouts."""
@@ -247,9 +254,10 @@ class GraphEncoder(DeviceOp):
                                        C.c_void_p(sh))
         self._finish(rc, self.lib.lsm_gnn_backward_last_error, check,
                      "an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the encoder")
-        self._last_dweights = out["dweights"]
+        self._last_dweights, self._last_embed = out["dweights"], False
         if embed:   # the same stream: seeded by this call's dh0, into the EmbedConv range of the same dweights
             self._run_embed_backward(node_obs, adj, masks, B, E, N, out["dh0"], out["dweights"], check)
+            self._last_embed = True   # only once the embed call went through: the range holds a gradient
         return {"dweights": out["dweights"], "dh0": out["dh0"] if dh0 else None}
 
     def backward(self, node_obs, adj, dout, agent_id=None, dh0: bool = False, check: bool = False,

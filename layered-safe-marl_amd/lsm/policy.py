@@ -16,8 +16,10 @@ the stored action, the entropy and the values come back. ``DevicePolicy.ppo_loss
 gradient at the logits and the values (``lsm.loss``). ``PolicyHead.backward`` and
 ``DevicePolicy.heads_backward`` carry those two gradients back through the heads (``csrc/lsm_backward.hip``
 through ``include/lsm_backward.h``): the gradient of every packed head weight (``PolicyHead.gradients``) and
-the gradient at the encoder's output. No backward pass through the encoders, Discrete action spaces only, and
-no CPU fallback, as elsewhere in the project.
+the gradient at the encoder's output; ``DevicePolicy.encoders_backward`` continues through the encoders,
+``DevicePolicy.optimizer_step`` clips and steps both networks on the device (``lsm.optim``), and
+``DevicePolicy.ppo_update`` chains the whole update without a host read. Discrete action spaces only, and no CPU
+fallback, as elsewhere in the project.
 
 Sampling is ``Categorical.sample`` as a distribution -- the inverse CDF of ``torch.rand`` uniforms -- not
 torch's generator stream: the same seed does not reproduce ``torch.multinomial``'s actions.
@@ -153,6 +155,13 @@ class PolicyHead(DeviceOp):
     def load(self, state_dict, prefix: str = ""):
         """Refresh the blob from a GR_Actor / GR_Critic state dict (after each optimiser step)."""
         self._set(pack_head_weights(state_dict, self.cfg, prefix))
+
+    def state_dict(self, prefix: str = ""):
+        """The current device blob as {name: float32 tensor}, the inverse of load (unpack_head_weights; one
+        download): a checkpoint after lsm.optim.DeviceAdam's steps needs no torch module."""
+        torch = _torch()
+        blob = self.weights.cpu().numpy()
+        return {k: torch.from_numpy(v) for k, v in unpack_head_weights(blob, self.cfg, prefix).items()}
 
     def _inputs(self, x0, x1, rnn_states, masks, T, shape, who):
         """forward's and evaluate's (R, x0, x1, rnn_states, masks) after their checks: R rows, taken from x1,
@@ -609,3 +618,46 @@ class DevicePolicy:
                 raise PolicyError("heads_out has no %s dx1: call heads_backward(..., dx=True)" % who)
             out[who] = enc.backward(mb["node_obs"], mb["adj"], h["dx1"], mb["agent_id"], dh0=dh0, embed=embed)
         return out
+
+    def _check_optimisers(self, actor_opt, critic_opt, update_actor):
+        for opt, mods, who in ((actor_opt, (self.actor_encoder, self.actor_head), "actor"),
+                               (critic_opt, (self.critic_encoder, self.critic_head), "critic")):
+            if who == "actor" and not update_actor:
+                continue
+            held = getattr(opt, "modules", None)
+            if held is None or len(held) != 2 or held[0] is not mods[0] or held[1] is not mods[1]:
+                raise PolicyError("%s_opt must be a DeviceAdam over [%s_encoder, %s_head] of this policy"
+                                  % (who, who, who))
+
+    def optimizer_step(self, actor_opt, critic_opt, update_actor: bool = True):
+        """The last lines of each half of GR_MAPPO.ppo_update: the gradient norm, clip_grad_norm_ and
+        optimizer.step() of both networks in one lsm_optim_step call (lsm.optim, include/lsm_optim.h) on the
+        gradients encoders_backward(embed=True) and heads_backward just left: three launches, no host
+        synchronisation. actor_opt / critic_opt: DeviceAdam over [actor_encoder, actor_head] /
+        [critic_encoder, critic_head]. The blobs are updated in place: the next evaluate_actions / get_actions
+        reads the new weights. update_actor=False: the critic's group alone; the actor's weights, moments and
+        state are untouched, as with torch's None gradients. Returns {'actor': ..., 'critic': ...}, each
+        DeviceAdam.step's dict of 0-dim device views ('actor' None without update_actor)."""
+        from . import optim
+        self._check_optimisers(actor_opt, critic_opt, update_actor)
+        return optim.optimizer_step(actor_opt, critic_opt, update_actor)
+
+    def ppo_update(self, mb, loss, value_norm, actor_opt, critic_opt, data_chunk_length=None,
+                   update_actor: bool = True):
+        """GR_MAPPO.ppo_update on one minibatch, end to end on the device: ppo_loss, heads_backward(dx=True),
+        encoders_backward(embed=True) and optimizer_step, a fixed sequence of launches with no host read
+        anywhere. Returns the reference's tuple as a dict of device tensors, valid until the next call:
+        value_loss, critic_grad_norm, policy_loss, dist_entropy, actor_grad_norm (0-dim), imp_weights [L*C, 1],
+        and skipped = {'actor', 'critic'} (0-dim, 1 where a non-finite gradient left that network untouched).
+        Without update_actor the actor's entries (policy_loss, dist_entropy, imp_weights too) are None."""
+        self._check_optimisers(actor_opt, critic_opt, update_actor)
+        out = self.ppo_loss(mb, loss, value_norm, data_chunk_length, update_actor=update_actor)
+        heads = self.heads_backward(mb, out, data_chunk_length, update_actor=update_actor, dx=True)
+        self.encoders_backward(mb, heads, update_actor=update_actor, embed=True)
+        from . import optim
+        st = optim.optimizer_step(actor_opt, critic_opt, update_actor)   # (checked above, before any launch)
+        a, c = st["actor"], st["critic"]
+        return {"value_loss": out.get("value_loss"), "critic_grad_norm": c["grad_norm"],
+                "policy_loss": out.get("policy_loss"), "dist_entropy": out.get("dist_entropy"),
+                "actor_grad_norm": a["grad_norm"] if a else None, "imp_weights": out.get("imp_weights"),
+                "skipped": {"actor": a["skipped"] if a else None, "critic": c["skipped"]}}
