@@ -52,6 +52,8 @@ UNITS = {
     "lsm_backward.hip": ["../../include/lsm_backward.h", "../../include/lsm_policy.h", "lsm_head_tile.h"],
     # the gradient norm, the clipping and Adam on the blobs (include/lsm_optim.h, likewise outside build_id())
     "lsm_optim.hip": ["../../include/lsm_optim.h"],
+    # GR_MAPPO.train's train_info accumulator (include/lsm_train_info.h, likewise outside build_id())
+    "lsm_train_info.hip": ["../../include/lsm_train_info.h"],
 }
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -1,8 +1,8 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
 ``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
 ``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h``, ``include/lsm_backward.h``,
-``include/lsm_gnn_backward.h``, ``include/lsm_gnn_embed_backward.h`` and ``include/lsm_optim.h``
-(``liblsm_rollout.so``).
+``include/lsm_gnn_backward.h``, ``include/lsm_gnn_embed_backward.h``, ``include/lsm_optim.h`` and
+``include/lsm_train_info.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
 INTEGRATION.md): plain pointers and sizes only, no torch types cross the ABI.
@@ -89,6 +89,13 @@ EXPORTED_GNN_EMBED_BACKWARD = ("lsm_gnn_embed_floats", "lsm_gnn_embed_backward_w
 # Every symbol include/lsm_optim.h declares (checked by tests/test_optim_capi.py).
 EXPORTED_OPTIM = ("lsm_optim_workspace_bytes", "lsm_optim_step", "lsm_host_optim_step", "lsm_optim_last_error")
 LSM_OPT_MAX_GROUPS, LSM_OPT_MAX_SEGMENTS, LSM_OPT_CHUNK, LSM_OPT_LANES = 4, 8, 1024, 256
+# Every symbol include/lsm_train_info.h declares (checked by tests/test_train_info_capi.py).
+EXPORTED_TRAIN_INFO = ("lsm_train_info_add", "lsm_train_info_mean", "lsm_host_train_info_add",
+                       "lsm_host_train_info_mean", "lsm_train_info_last_error")
+LSM_TRAIN_INFO_SLOTS, LSM_TRAIN_INFO_MEANS, LSM_TRAIN_INFO_STATE_WORDS, LSM_TRAIN_INFO_LANES = 8, 6, 18, 64
+# the slots' names, in the header's order
+TRAIN_INFO_SLOTS = ("value_loss", "policy_loss", "dist_entropy", "actor_grad_norm", "critic_grad_norm", "ratio",
+                    "actor_skipped", "critic_skipped")
 
 
 class LsmConfig(C.Structure):
@@ -256,6 +263,11 @@ class LsmOptimGroup(C.Structure):
                 [("state", C.c_void_p), ("info", C.c_void_p)])
 
 
+class LsmTrainInfoSrc(C.Structure):
+    """lsm_train_info_src (include/lsm_train_info.h), passed by value."""
+    _fields_ = [("value", C.c_void_p * LSM_TRAIN_INFO_SLOTS)]
+
+
 class LsmError(RuntimeError):
     pass
 
@@ -375,6 +387,12 @@ def load_library(path: str = LIB_PATH):
         "lsm_optim_step": (I32, [C.POINTER(LsmOptimGroup), I32, P, P]),
         "lsm_host_optim_step": (I32, [C.POINTER(LsmOptimGroup), I32, P]),
         "lsm_optim_last_error": (C.c_char_p, []),
+        # include/lsm_train_info.h
+        "lsm_train_info_add": (I32, [P, LsmTrainInfoSrc, I32, P]),
+        "lsm_train_info_mean": (I32, [P, I64, P, P]),
+        "lsm_host_train_info_add": (I32, [P, LsmTrainInfoSrc, I32]),
+        "lsm_host_train_info_mean": (I32, [P, I64, P]),
+        "lsm_train_info_last_error": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
