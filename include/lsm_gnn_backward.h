@@ -85,7 +85,7 @@
  * <q, w_e>, <dO, w_e> of the current one), plus 2 * round_up(E * E, 4) for the adjacency and its transpose when
  * that still fits in the 163840 bytes of a workgroup. Nothing is stored per edge. A size whose single graph
  * does not fit is refused (reference defaults: 1444 bytes per node, accepted up to E = 113; the forward accepts
- * sizes this call refuses). G = min(256 / TS, what fits).
+ * sizes this call refuses, and lsm_gnn_backward_large.h runs this pass at them). G = min(256 / TS, what fits).
  *
  * Workspace: 0 bytes per graph; per slab one float64 row of the conv layers' entries,
  *   8 * ceil(B / LSM_GNN_BWD_SLAB) * (lsm_gnn_weights_floats(cfg) - offset of conv layer 0) bytes

@@ -36,8 +36,10 @@ UNITS = {
     # the fused graph-encoder forward (include/lsm_gnn.h, likewise outside build_id())
     "lsm_gnn.hip": ["../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
     # the encoder's backward: readout and conv layers (include/lsm_gnn_backward.h, likewise outside build_id());
-    # lsm_gnn_tile.h holds the per-graph forward text the two units share
-    "lsm_gnn_backward.hip": ["../../include/lsm_gnn_backward.h", "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
+    # lsm_gnn_tile.h holds the per-graph forward text the two units share. The unit also holds the spilled tier
+    # of the same per-graph text (include/lsm_gnn_backward_large.h)
+    "lsm_gnn_backward.hip": ["../../include/lsm_gnn_backward.h", "../../include/lsm_gnn_backward_large.h",
+                             "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],
     # EmbedConv's backward, from dh0 (include/lsm_gnn_embed_backward.h, likewise outside build_id())
     "lsm_gnn_embed_backward.hip": ["../../include/lsm_gnn_embed_backward.h", "../../include/lsm_gnn_backward.h",
                                    "../../include/lsm_gnn.h", "lsm_gnn_tile.h"],

@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI in ``include/lsm_rollout.h``, ``include/lsm_learner.h``,
 ``include/lsm_recurrent.h``, ``include/lsm_minibatch_edges.h``, ``include/lsm_gnn.h``,
 ``include/lsm_policy.h``, ``include/lsm_evaluate.h``, ``include/lsm_loss.h``, ``include/lsm_backward.h``,
-``include/lsm_gnn_backward.h``, ``include/lsm_gnn_embed_backward.h``, ``include/lsm_optim.h`` and
+``include/lsm_gnn_backward.h``, ``include/lsm_gnn_backward_large.h``, ``include/lsm_gnn_embed_backward.h``,
+``include/lsm_optim.h`` and
 ``include/lsm_train_info.h`` (``liblsm_rollout.so``).
 
 This is the Python stub a maintainer of the reference would add (see
@@ -81,6 +82,10 @@ LSM_BWD_SLAB = 2048
 EXPORTED_GNN_BACKWARD = ("lsm_gnn_backward_workspace_bytes", "lsm_gnn_backward", "lsm_host_gnn_backward",
                          "lsm_gnn_backward_plan", "lsm_gnn_backward_last_error")
 LSM_GNN_BWD_SLAB = 256
+# Every symbol include/lsm_gnn_backward_large.h declares (checked by tests/test_gnn_backward_large_capi.py).
+EXPORTED_GNN_BACKWARD_LARGE = ("lsm_gnn_backward_large_workspace_bytes", "lsm_gnn_backward_large",
+                               "lsm_host_gnn_backward_large", "lsm_gnn_backward_large_plan",
+                               "lsm_gnn_backward_large_last_error")
 # Every symbol include/lsm_gnn_embed_backward.h declares (checked by tests/test_gnn_embed_backward_capi.py); its
 # slabs are LSM_GNN_BWD_SLAB graphs.
 EXPORTED_GNN_EMBED_BACKWARD = ("lsm_gnn_embed_floats", "lsm_gnn_embed_backward_workspace_bytes",
@@ -184,6 +189,13 @@ class LsmGnnBwdLaunchPlan(C.Structure):
     """lsm_gnn_bwd_launch_plan (include/lsm_gnn_backward.h): what lsm_gnn_backward_plan fills."""
     _fields_ = ([(n, C.c_int32) for n in ("TS", "G", "fast", "adj_lds", "acc_lds", "SA", "SK", "ST")] +
                 [(n, C.c_int64) for n in ("lds_bytes", "slabs", "ws_bytes")])
+
+
+class LsmGnnBwdLargeLaunchPlan(C.Structure):
+    """lsm_gnn_bwd_large_launch_plan (include/lsm_gnn_backward_large.h): what lsm_gnn_backward_large_plan fills."""
+    _fields_ = ([(n, C.c_int32) for n in ("TS", "G", "fast", "adj_lds", "acc_lds", "SA", "SK", "ST", "spill",
+                                          "spilled_floats")] +
+                [(n, C.c_int64) for n in ("lds_bytes", "slabs", "ws_bytes", "scratch_bytes")])
 
 
 class LsmGnnEmbedBwdIo(C.Structure):
@@ -375,6 +387,13 @@ def load_library(path: str = LIB_PATH):
         "lsm_host_gnn_backward": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32]),
         "lsm_gnn_backward_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, C.POINTER(LsmGnnBwdLaunchPlan)]),
         "lsm_gnn_backward_last_error": (C.c_char_p, []),
+        # include/lsm_gnn_backward_large.h
+        "lsm_gnn_backward_large_workspace_bytes": (SZ, [LsmGnnConfig, I64, I32, I32]),
+        "lsm_gnn_backward_large": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32, I32, P]),
+        "lsm_host_gnn_backward_large": (I32, [LsmGnnConfig, P, C.POINTER(LsmGnnBwdIo), I64, I32, I32]),
+        "lsm_gnn_backward_large_plan": (I32, [LsmGnnConfig, I64, I32, I32, I32, I32,
+                                              C.POINTER(LsmGnnBwdLargeLaunchPlan)]),
+        "lsm_gnn_backward_large_last_error": (C.c_char_p, []),
         # include/lsm_gnn_embed_backward.h (its slabs are LSM_GNN_BWD_SLAB graphs)
         "lsm_gnn_embed_floats": (SZ, [LsmGnnConfig]),
         "lsm_gnn_embed_backward_workspace_bytes": (SZ, [LsmGnnConfig, I64, I32]),

@@ -8,7 +8,7 @@ disconnect words) without expanding it. No edge list, no per-edge tensor and no 
 ``process_adj`` is not called. There is no CPU fallback, as elsewhere in the project.
 
 ``GraphEncoder.backward(node_obs, adj, dout, agent_id)`` (``csrc/lsm_gnn_backward.hip`` through
-``include/lsm_gnn_backward.h``) is the backward pass through the readout and the TransformerConv layers: from
+``include/lsm_gnn_backward.h`` and, beyond its LDS limit, ``include/lsm_gnn_backward_large.h``) is the backward pass through the readout and the TransformerConv layers: from
 the gradient at ``forward``'s output to the gradient of every conv-layer weight and to ``dh0``, the gradient at
 EmbedConv's output. ``GraphEncoder.embed_backward(node_obs, adj, dh0)`` (``csrc/lsm_gnn_embed_backward.hip`` through
 ``include/lsm_gnn_embed_backward.h``) is EmbedConv's own backward, from ``dh0`` to the gradient of the blob's
@@ -234,11 +234,16 @@ class GraphEncoder(DeviceOp):
     def _bwd_outputs(self, B, E):
         torch = _torch()
         n = int(self.lib.lsm_gnn_backward_workspace_bytes(self._struct, B, E))
-        if n == 0 and B > 0:
-            raise GnnError(self.lib.lsm_gnn_backward_last_error().decode())
+        # a size lsm_gnn_backward refuses (a graph beyond its LDS limit, or one nothing accepts) goes to the spilled
+        # tier, whose workspace also holds the scratch
+        large = n == 0 and B > 0
+        if large:
+            n = int(self.lib.lsm_gnn_backward_large_workspace_bytes(self._struct, B, E, 0))
+            if n == 0:
+                raise GnnError(self.lib.lsm_gnn_backward_large_last_error().decode())
         f32 = dict(dtype=torch.float32, device=self.device)
         return {"dweights": torch.zeros(self._n, **f32), "dh0": torch.empty((B, E, self.cfg.embed_hidden), **f32),
-                "workspace": torch.empty(max(n // 8, 1), dtype=torch.float64, device=self.device)}
+                "workspace": torch.empty((n + 7) // 8 or 1, dtype=torch.float64, device=self.device), "large": large}
 
     def _run_backward(self, node_obs, adj, masks, B, E, N, dout, agent_id, dh0, check, embed=False):
         cfg = self.cfg
@@ -250,9 +255,15 @@ class GraphEncoder(DeviceOp):
         io = capi.LsmGnnBwdIo(node_obs=ptr(node_obs), adj=ptr(adj), masks=ptr(masks), agent_id=ptr(aid), dout=ptr(dout),
                               dweights=ptr(out["dweights"]), dh0=ptr(out["dh0"]) if dh0 or embed else None,
                               workspace=ptr(out["workspace"]), bad=ptr(self.bad))
-        rc = self.lib.lsm_gnn_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
-                                       C.c_void_p(sh))
-        self._finish(rc, self.lib.lsm_gnn_backward_last_error, check,
+        if out["large"]:
+            rc = self.lib.lsm_gnn_backward_large(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
+                                                 0, C.c_void_p(sh))
+            last_error = self.lib.lsm_gnn_backward_large_last_error
+        else:
+            rc = self.lib.lsm_gnn_backward(self._struct, C.c_void_p(self.weights.data_ptr()), C.byref(io), B, E, N,
+                                           C.c_void_p(sh))
+            last_error = self.lib.lsm_gnn_backward_last_error
+        self._finish(rc, last_error, check,
                      "an entity type outside [0, num_embeddings) or an agent_id outside [0, E) reached the encoder")
         self._last_dweights, self._last_embed = out["dweights"], False
         if embed:   # the same stream: seeded by this call's dh0, into the EmbedConv range of the same dweights
@@ -269,6 +280,10 @@ class GraphEncoder(DeviceOp):
         weight in the blob's own layout, overwritten, not accumulated, 0 over EmbedConv's entries (gradients()
         names them) -- and, with dh0=True, dh0 [B, E, embed_hidden], the gradient at EmbedConv's output (None
         otherwise). The workspace (one float64 row of the conv entries per 256 graphs) is cached with them.
+        Every size forward accepts is accepted: where a graph's backward does not fit one workgroup's LDS
+        (lsm_gnn_backward's limit, E = 113 at the defaults) the call goes to lsm_gnn_backward_large
+        (``include/lsm_gnn_backward_large.h``), which keeps part of a graph's buffers in a scratch behind the
+        workspace; the result and the number of launches are the same.
         embed=True: EmbedConv's backward (embed_backward) follows on the same stream, two more launches, seeded
         by this call's dh0 (produced internally whatever dh0= says) and writing the EmbedConv range of the same
         dweights, which is then the complete gradient. embed=False: the EmbedConv range is 0."""

@@ -601,7 +601,8 @@ class DevicePolicy:
         critic_encoder.gradients(), and with dh0=True each dict's dh0 is the gradient at EmbedConv's output.
         embed=True: GraphEncoder.embed_backward follows each call on the same stream, seeded by that dh0 (two more
         launches per encoder), and gradients() then names every encoder weight's gradient, EmbedConv's included;
-        by default the EmbedConv entries are 0, as before."""
+        by default the EmbedConv entries are 0, as before. Every graph size the encoders' forward accepts is
+        accepted (GraphEncoder.backward goes to the spilled tier beyond lsm_gnn_backward's LDS limit)."""
         if self.last_head_inputs is None:
             raise PolicyError("heads_backward follows ppo_loss or evaluate_actions on the same minibatch")
         if self.actor_encoder is self.critic_encoder:

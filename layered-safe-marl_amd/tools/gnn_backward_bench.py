@@ -12,8 +12,13 @@ the gradient at the encoder's output to every conv-layer weight's gradient and d
 
 Shapes: tools/gnn_bench.py's, 4096 envs x 8 agents (B = 32768 graphs, E = 24) in both adjacency layouts and 128
 envs x 64 agents (B = 8192, E = 192); the reference's default network; the actor's readout ('node') and the
-critic's ('global' mean). A size the backward refuses (its LDS need per graph: include/lsm_gnn_backward.h) is
-recorded with the refusal's text and not timed.
+critic's ('global' mean). E = 192 is beyond lsm_gnn_backward's LDS limit and runs through the spilled tier
+(include/lsm_gnn_backward_large.h); each row records the plan (the spill level, G, the LDS and the scratch) and the
+time per graph. A size even that refuses is recorded with the refusal's text and not timed.
+
+  (C) the price of spilling where both exist: at 4096 x 8, E = 24, lsm_gnn_backward_large with min_spill = 0
+      (lsm_gnn_backward's own kernel) against min_spill = 4 (only the forward's region left in LDS) on the same
+      inputs, checked bit-equal first, in alternating rounds.
 
 Method: both sides are run once and checked first, by the tests' criterion on the first 8 envs' graphs: the same
 torch ops in float64 are the truth, e32 is the float32 torch path's error against it per gradient tensor, and a
@@ -21,7 +26,7 @@ fused error above 4 * e32 + 4 * 2^-23 * max|truth| ends the run. Then a warm-up,
 `reps` back-to-back calls, the sides in alternating rounds, and the median / min / max of the rounds' means
 (tools/bench_common.py's alternated()).
 
-    python layered-safe-marl_amd/tools/gnn_backward_bench.py [--out FILE] [--quick] [--only small|large]
+    python layered-safe-marl_amd/tools/gnn_backward_bench.py [--out FILE] [--quick] [--only small|large|spill]
 """
 from __future__ import annotations
 
@@ -117,6 +122,74 @@ def torch_gradients(cfg, p, h0, B, E, edge_list, agent_id, dout):
     return res
 
 
+def large_plan(lib, cfg, B, E, min_spill=0):
+    import ctypes as C
+    from lsm import capi
+    p = capi.LsmGnnBwdLargeLaunchPlan()
+    if lib.lsm_gnn_backward_large_plan(cfg.struct(), B, E, 1, 0, min_spill, C.byref(p)):
+        return {"refused": lib.lsm_gnn_backward_large_last_error().decode()}
+    return {n: int(getattr(p, n)) for n, _ in p._fields_}
+
+
+def bench_spill(envs, agents, quick):
+    """(C): level 0 against level 4 through the C ABI, on a step's graphs in the reference layout."""
+    import ctypes as C
+    import torch
+    from lsm import capi, gnn, hj_tables
+    from lsm.config import EnvArgs
+    from lsm.vec_env import GpuGraphVecEnv
+    args = EnvArgs(dynamics_type="double_integrator", num_agents=agents, num_landmarks=2, world_size=4,
+                   episode_length=250, num_env_steps=1000, use_safety_filter=True, seed=0)
+    vt = hj_tables.default_tables("double_integrator", small=True)[0]
+    env = GpuGraphVecEnv(args, num_envs=envs, device=DEV, value_table=vt, return_numpy=False, build_infos=False,
+                         adj_layout="reference")
+    env.reset(0)
+    g = torch.Generator(device=DEV).manual_seed(3)
+    for _ in range(5):
+        env.step(torch.randint(0, 25, (envs, agents), generator=g, device=DEV, dtype=torch.int32), 0)
+    B, E, F = envs * agents, env.E, env.F
+    node = env.t_node.view(B, E, F).contiguous()
+    dense = env.reference_adj().reshape(B, E, E).contiguous()
+    aid = env.agent_id.view(B).long().contiguous()
+    lib = capi.load_library()
+    res = {"envs": envs, "agents": agents, "layout": "reference", "B": B, "E": E}
+    for role, aggr in (("actor", "node"), ("critic", "global_mean")):
+        cfg = gnn.GnnConfig(F=F, aggr=aggr)
+        enc = gnn.GraphEncoder(cfg, gnn.pack_weights(seeded_state_dict(cfg), cfg, prefix=""), DEV)
+        dout = torch.randn((B, cfg.out_dim), generator=g, device=DEV)
+        bad = torch.zeros(1, dtype=torch.int64, device=DEV)
+        sides, outs, plans = {}, {}, {}
+        for k in (0, 4):
+            n = int(lib.lsm_gnn_backward_large_workspace_bytes(cfg.struct(), B, E, k))
+            o = {"dweights": torch.zeros(enc.weights.numel(), device=DEV), "dh0": torch.empty((B, E, cfg.embed_hidden), device=DEV),
+                 "workspace": torch.empty((n + 7) // 8, dtype=torch.float64, device=DEV)}
+            io = capi.LsmGnnBwdIo(node_obs=node.data_ptr(), adj=dense.data_ptr(), masks=None,
+                                  agent_id=aid.data_ptr() if aggr == "node" else None, dout=dout.data_ptr(),
+                                  dweights=o["dweights"].data_ptr(), dh0=o["dh0"].data_ptr(),
+                                  workspace=o["workspace"].data_ptr(), bad=bad.data_ptr())
+
+            def run(k=k, io=io):
+                rc = lib.lsm_gnn_backward_large(cfg.struct(), C.c_void_p(enc.weights.data_ptr()), C.byref(io), B, E, 1, k,
+                                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+                if rc:
+                    raise RuntimeError(lib.lsm_gnn_backward_large_last_error().decode())
+            run()
+            outs[k], plans[k] = o, large_plan(lib, cfg, B, E, k)
+            sides["level%d" % k] = (run, 3 if quick else 10)
+        torch.cuda.synchronize()
+        for nm in ("dweights", "dh0"):
+            if not torch.equal(outs[0][nm].view(torch.int32), outs[4][nm].view(torch.int32)):
+                raise SystemExit("level 4 differs from level 0 in %s (%s)" % (nm, role))
+        t = alternated(sides)
+        res[role] = dict(t, plan_level0=plans[0], plan_level4=plans[4], bit_equal=True,
+                         ratio_level4_over_level0=t["level4"]["median"] / t["level0"]["median"])
+        print("%d x %d spill %s: level 0 %.3f ms [%.3f, %.3f], level 4 %.3f ms [%.3f, %.3f] (x%.2f)" % (
+            envs, agents, role, t["level0"]["median"], t["level0"]["min"], t["level0"]["max"], t["level4"]["median"],
+            t["level4"]["min"], t["level4"]["max"], res[role]["ratio_level4_over_level0"]), file=sys.stderr, flush=True)
+    env.close()
+    return res
+
+
 def bench_env(envs, agents, layout, quick, enforce=True):
     import torch
     from lsm import edges, gnn, hj_tables
@@ -187,8 +260,9 @@ def bench_env(envs, agents, layout, quick, enforce=True):
         for fn, _ in sides.values():   # warm-up
             fn()
         t = alternated(sides)
-        plan = {"slabs": (B + 255) // 256}
+        plan = large_plan(enc.lib, cfg, B, E)
         res[role] = dict(t, checked_graphs=nb, worst_tensor=worst, worst_check=chk[worst], plan=plan,
+                         fused_us_per_graph=1e3 * t["fused"]["median"] / B,
                          ratio_torch_forward_backward_over_fused=t["torch_forward_backward"]["median"] / t["fused"]["median"])
         print("%d x %d %s %s: fused %.3f ms [%.3f, %.3f], torch forward + backward %.3f ms [%.3f, %.3f] (x%.2f), "
               "torch backward alone %.3f ms" % (
@@ -205,7 +279,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=PROFILE)
     ap.add_argument("--quick", action="store_true", help="fewer calls per round")
-    ap.add_argument("--only", default=None, help="'small' (E = 24) or 'large' (E = 192)")
+    ap.add_argument("--only", default=None, help="'small' (E = 24), 'large' (E = 192) or 'spill' (level 0 against 4)")
     ap.add_argument("--record-only", action="store_true", help="record the criterion's figures without ending the run on a miss")
     a = ap.parse_args()
     runs = []
@@ -214,7 +288,10 @@ def main():
                  bench_env(4096, 8, "compact", a.quick, not a.record_only)]
     if a.only in (None, "large"):
         runs += [bench_env(128, 64, "compact", a.quick, not a.record_only)]
-    emit({"gnn_backward_bench": runs}, a.out)
+    out = {"gnn_backward_bench": runs}
+    if a.only in (None, "small", "spill"):
+        out["gnn_backward_spill_bench"] = [bench_spill(4096, 8, a.quick)]
+    emit(out, a.out)
 
 
 if __name__ == "__main__":
